@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the DDPM hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode bf16|fp32] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode bf16|fp32] [--batch B] [--dump-outputs DIR] [--full]
 
 W warm-up steps (after `--prewarm` set-up steps that absorb the process's cold start), then exactly K timed steps.
 A "step" is one full training step of BASELINE cfg 2 (DDPM on CIFAR-10 32x32, UNet base 128,
 mults 1-2-4, T=1000, L1 loss, Adam lr 1e-4) on a synthetic batch of B=128 images per GPU that is
 already resident in HBM: draw t and eps on the device, q_sample, UNet forward, loss, UNet
 backward, gradient all-reduce (N>1, RCCL, overlapped with backward), fused Adam.  Nothing is
-skipped or cached between steps.  The denoise rate (hipGraph-replayed p_sample at B=64) is
-reported beside it.  One JSON line is printed by rank 0.
+skipped or cached between steps.  One JSON line (the record) is printed by rank 0.
+
+`--dump-outputs DIR` runs the timed step once more from the run's seeded initial state and writes what it returned (dump_outputs),
+so two runs or two builds with the same arguments can be compared output for output.  `--full` measures the rest after the timed steps: the denoise rate
+(hipGraph-replayed p_sample at B=64), the per-kernel roofline, the exposed all-reduce, the fp32-mode, cfg-3 and data-parallel legs
+and the CPU baseline; their numbers go into the record and into a "detail" line printed before it.
 
 N>1: one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the ranks come from
 the environment; a bare `python bench.py --gpus N` (no RANK in the environment) re-launches itself under torch.distributed.run
@@ -186,6 +190,43 @@ def timed_leg(step, steps, warmup, sync, world, device="cpu"):
     return float(el) / steps * 1e3
 
 
+def initial_state(net, dev):
+    """What --dump-outputs restores: the seeded weights before the first step and the device generator's state."""
+    return net.flat_params.detach().clone(), torch.cuda.get_rng_state(dev)
+
+
+def dump_outputs(out_dir, step, net, opt, start, dev, write=True, sample=1 << 22):
+    """--dump-outputs: the timed training step run once more from the run's initial state, and what it hands its caller -- the loss
+    it returns, the fp32 master weights Adam updated, the gradient it computed -- as float32 DIR/loss.npy, params.npy, grads.npy.
+    Why not the last timed step's own state: each step starts from weights and Adam moments that every earlier step shaped, and the
+    step's fp32 atomics add in an order that changes from run to run.  Adam turns that rounding in the near-cancelling gradients
+    (the biases in front of a GroupNorm, tools/bias_grad_amplification.py) into full-size updates, so after ~150 steps two runs differ
+    by ~1 % in the loss.  Restored in place (a captured graph keeps reading the same buffers): the seeded weights, zero moments, step
+    count 0, the device generator (the step draws the first step's t and eps); `step` is the callable the timed loop ran, on the same
+    batch.  Every rank runs it (collectives); `write` on rank 0.  A flat buffer of more than `sample` elements is written as those of
+    its elements at a fixed, seeded set of indices (the same in every run): 2 x 16 MB at most."""
+    import numpy as np
+    p0, rng0 = start
+    with torch.no_grad():
+        net.flat_params.copy_(p0)
+    net.mark_params_dirty()
+    sd = opt.state_dict()
+    sd.update(step=0, m=None, v=None)
+    opt.load_state_dict(sd)
+    torch.cuda.set_rng_state(rng0, dev)
+    loss = step(0)
+    torch.cuda.synchronize(dev)
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "params": net.flat_params.detach(), "grads": net.flat_grads.detach()}
+    for name, a in arrays.items():
+        if a.numel() > sample:
+            g = torch.Generator().manual_seed(0)
+            a = a[torch.randint(0, a.numel(), (sample,), generator=g).sort().values.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+
+
 def dry_run_cpu(args, world, rank):
     """Launch plumbing on the host: gloo ranks, a stand-in step (bucketed all-reduce over a small flat buffer + a sleep),
     barrier-bracketed timing, MAX over ranks, rank 0 prints the line.  No kernels run; nothing here is a measurement -- but the
@@ -196,7 +237,7 @@ def dry_run_cpu(args, world, rank):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")
-    elif not args.no_extras:                               # N = 1 through the data-parallel code path (a one-rank group)
+    elif args.full and not args.no_extras:                 # N = 1 through the data-parallel code path (a one-rank group)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", str(29500 + os.getpid() % 400))
         dist.init_process_group("gloo", rank=0, world_size=1)
         solo_group = True
@@ -233,7 +274,7 @@ def dry_run_cpu(args, world, rank):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     ways = None
-    if red is not None:
+    if red is not None and args.full:
         ways = {"segmented_graph": round(float(el) / args.steps * 1e3, 3), "eager_overlap": round(timed_leg(step, 2, 1, sync, world), 3)}
         red.defer = True
         ways["eager_allreduce_after_backward"] = round(timed_leg(step, 2, 1, sync, world), 3)
@@ -367,8 +408,16 @@ def main():
     ap.add_argument("--mode", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--batch", type=int, default=128, help="images per GPU (reference default 128)")
     ap.add_argument("--denoise-steps", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: denoise rate, per-kernel roofline, "
+                         "exposed all-reduce, shader clock, the fp32-mode / cfg-3 / data-parallel legs, the CPU baseline (off: the "
+                         "run times the training step and prints the record alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more from the seeded initial state and write what it returned "
+                         "(loss, updated weights, gradients; see dump_outputs) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the fp32-mode leg, the named-kernel microbenchmark and the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the fp32-mode leg, the named-kernel microbenchmark and the CPU baseline")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("MI_BENCH_GRAPH", "-1")),
                     help="1: replay the training step as a hipGraph (under data parallelism: a chain of graphs cut at the gradient "
                          "buckets), 0: eager, -1 (default): the Trainer's default = replay, eager if the capture fails")
@@ -379,6 +428,9 @@ def main():
     ap.add_argument("--sweep-channels", action="store_true",
                     help="self-launching form only: run the N-rank bench for NCCL_MAX_NCHANNELS in {default, 8, 16} and report all three")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
 
     if os.environ.get("MI_BENCH_UNSET_NCHANNELS") == "1":
         os.environ.pop("NCCL_MAX_NCHANNELS", None)
@@ -435,6 +487,7 @@ def main():
         opt.grad_scale = reducer.grad_scale
 
     B = args.batch
+    start = initial_state(net, dev) if args.dump_outputs else None
     gen = torch.Generator(device=dev).manual_seed(1234 + rank)
     imgs = torch.rand(B, 3, SIDE, SIDE, device=dev, generator=gen) * 2 - 1    # synthetic [-1,1] batch, HBM resident
     batch = (imgs, None)
@@ -494,7 +547,7 @@ def main():
         elapsed = float(el)
     # the shader clock right behind the timed steps (the chip is in its sustained state: a probe after an idle stretch reads 10 - 15 % low)
     sclk = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         try:
             sclk = K.clock_probe(dev, usec=300)
         except Exception:                                   # noqa: BLE001
@@ -513,10 +566,12 @@ def main():
         raise SystemExit(f"bench.py: non-finite training state after the timed steps (loss {final_loss}); no throughput is reported")
     ms_per_step = elapsed / args.steps * 1e3
     images_per_s = world * B * args.steps / elapsed
+    if args.dump_outputs:                               # the --full legs below then start from the state this leaves
+        dump_outputs(args.dump_outputs, train_step, net, opt, start, dev, write=rank == 0)
 
     # ---- exposed all-reduce time: GPU time on the compute stream between the end of backward and the start of Adam
     comm = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         waits = []
         for i in range(5):
             reducer.begin()
@@ -549,33 +604,35 @@ def main():
         comm["ways_ms"] = ways
 
     # ---- denoise rate: hipGraph-replayed reverse step at B=64 (ddpm.py:520 samples 64 images)
-    from src.runtime.sampler import GraphSampler
-    model.eval()
-    gs = GraphSampler(model.diffusion_model, (64, 3, SIDE, SIDE))
-    gs._capture()
-    gs.set_image(torch.randn_like(gs.x)); gs.t.fill_(999)
-    # (60 untimed replays first: from idle the chip's shader clock takes tens of milliseconds of load to reach its sustained value --
-    #  tools/proto/clock_probe.py: 2 050 MHz in the first millisecond, 2 390 after ~30 ms -- and a T = 1000 sampling run lasts a second)
-    for _ in range(60):
-        gs.z.normal_(); gs.graph.replay()
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(args.denoise_steps):
-        gs.z.normal_(); gs.graph.replay()
-    sync()
-    den = time.perf_counter() - t0
-    if use_dist:
-        el = torch.tensor([den], device=dev, dtype=torch.float64)
-        dist.all_reduce(el, op=dist.ReduceOp.MAX)
-        den = float(el)
-    denoise_steps_per_s = world * args.denoise_steps / den
-    model.train()
+    denoise_steps_per_s = None
+    if args.full:
+        from src.runtime.sampler import GraphSampler
+        model.eval()
+        gs = GraphSampler(model.diffusion_model, (64, 3, SIDE, SIDE))
+        gs._capture()
+        gs.set_image(torch.randn_like(gs.x)); gs.t.fill_(999)
+        # (60 untimed replays first: from idle the chip's shader clock takes tens of milliseconds of load to reach its sustained value --
+        #  tools/proto/clock_probe.py: 2 050 MHz in the first millisecond, 2 390 after ~30 ms -- and a T = 1000 sampling run lasts a second)
+        for _ in range(60):
+            gs.z.normal_(); gs.graph.replay()
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.denoise_steps):
+            gs.z.normal_(); gs.graph.replay()
+        sync()
+        den = time.perf_counter() - t0
+        if use_dist:
+            el = torch.tensor([den], device=dev, dtype=torch.float64)
+            dist.all_reduce(el, op=dist.ReduceOp.MAX)
+            den = float(el)
+        denoise_steps_per_s = world * args.denoise_steps / den
+        model.train()
 
     # ---- per-kernel times of the step: HIP events (on the launch stream) around every library launch of three further EAGER
     #      training steps; a launch's time is the smallest of its measurements; symbols carry the template arguments rocprofv3
     #      prints.  The contraction and the partial-tile reduce of the weight-gradient kernel are timed as separate launches.
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         runs = []
         for i in range(3):
             K.PROBE = []
@@ -622,14 +679,14 @@ def main():
                 "avg_gflop_per_launch": round(fl / cnt / 1e9, 3), "avg_algorithmic_mb_per_launch": round(nb / cnt / 1e6, 2),
                 "probed_ms_per_step": round(sum(v[1] for v in agg.values()) * 1e3, 3),
                 "all_kernels": table}
-        if not args.no_extras and args.cfg == 2:
+        if extras and args.cfg == 2:
             roof["named_kernel"] = named_kernel_line(K, dev)
             # ... and at the one shape of the benchmarked configurations that SURVEY 8(d)(iv) calls HBM-bound: cfg 3's first level
             try:
                 roof["named_kernel_cfg3_level0"] = named_kernel_line(K, dev, 32, 64, 64, 64)
             except Exception as exc:                        # noqa: BLE001  (an extra entry: reported, never fatal)
                 roof["named_kernel_cfg3_level0"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
-    elif world > 1:
+    elif world > 1 and args.full:
         for i in range(3):
             eager_step(i)
     sync()
@@ -637,7 +694,7 @@ def main():
     # ---- N = 1 through the data-parallel code path (one-rank RCCL group, bucketed reducer, segmented graph): what SCALE's N = 1
     #      line would read if the driver launched it under torch.distributed.run, next to the plain single-process number above
     dp_path = None
-    if world == 1 and not use_dist and not args.no_extras:
+    if world == 1 and not use_dist and extras:
         # (RCCL prints a version banner through C stdio when its first communicator comes up: this leg's stdout goes to stderr, so that
         #  the N = 1 run keeps printing exactly one line)
         sys.stdout.flush()
@@ -672,7 +729,7 @@ def main():
 
     # ---- the parity-carrying fp32 mode (exact-fp32 MFMA), a short driver-timed leg
     fp32_mode = None
-    if rank == 0 and world == 1 and not args.no_extras and args.mode != "fp32":
+    if rank == 0 and world == 1 and extras and args.mode != "fp32":
         del gs
         m32, n32, o32 = build("fp32")
         for i in range(6):
@@ -707,7 +764,7 @@ def main():
     # ---- BASELINE configs[2] at its per-GPU batch (CelebA 64x64, UNet 64 / 1-2-4-8, B = 256 / 8 GPUs = 32): a short graph-replayed leg,
     #      so that the driver's record carries a cfg-3 number too (its own line: python bench.py --cfg 3 --batch 32)
     cfg3 = None
-    if rank == 0 and world == 1 and not args.no_extras and args.cfg == 2 and args.mode == "bf16":
+    if rank == 0 and world == 1 and extras and args.cfg == 2 and args.mode == "bf16":
         try:
             from src.runtime.graphed import GraphedTrainStep
             m3, n3, o3 = build("bf16", 3)
@@ -726,7 +783,7 @@ def main():
             cfg3 = {"error": f"{type(exc).__name__}: {exc}"[:300]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_extras and args.cfg == 2:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and extras and args.cfg == 2:
         cpu = cpu_baseline()
 
     if rank == 0:
@@ -760,8 +817,8 @@ def main():
                        "per_gpu_batch": B, "global_batch": B * world, "parallelism": f"dp{world}",
                        "step_launch": ("hipGraph replay" if use_graph else "eager") + (f" [{graph_note}]"[:60] if graph_note else ""),
                        # BASELINE's metric has two halves; the second one (hipGraph-replayed reverse-diffusion step at B = 64):
-                       "denoise_steps_per_sec": round(denoise_steps_per_s, 2), "denoise_batch": 64,
-                       "denoise_tflops": round(denoise_steps_per_s * 64 * FWD_GF / 1e3, 1),
+                       "denoise_steps_per_sec": round(denoise_steps_per_s, 2) if args.full else None, "denoise_batch": 64,
+                       "denoise_tflops": round(denoise_steps_per_s * 64 * FWD_GF / 1e3, 1) if args.full else None,
                        "train_tflops": round(images_per_s * TRAIN_GF / 1e3, 1),
                        "dp_path_n1_images_per_sec": (dp_path or {}).get("value"),
                        "fp32_mode_images_per_sec": (fp32_mode or {}).get("value"),
@@ -787,6 +844,9 @@ def main():
             ctypes.CDLL(None).fflush(None)
         except Exception:       # noqa: BLE001
             pass
+        if not args.full:                               # a plain run prints the record alone
+            print(json.dumps(out), flush=True)
+    if rank == 0 and args.full:
         print(json.dumps(detail), flush=True)
         try:            # the full report in one object (the layout tools/update_design_table.py and update_profiles_readme.py read)
             if os.path.isdir(os.path.join(ROOT, "gpurun_out")):

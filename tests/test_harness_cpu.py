@@ -286,7 +286,7 @@ def test_bench_self_launches_ranks_without_torchrun():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--full", "--steps", "3", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -303,19 +303,19 @@ def test_bench_self_launches_ranks_without_torchrun():
 
 
 def test_bench_dry_run_n1_runs_the_data_parallel_path_and_the_channel_sweep_relaunches():
-    """N = 1 also reports a leg through the data-parallel code path (one-rank group); `--sweep-channels` runs the N-rank bench once
+    """N = 1 with --full also reports a leg through the data-parallel code path (one-rank group); `--sweep-channels` runs the N-rank bench once
     per NCCL_MAX_NCHANNELS in {default, 8, 16} and prints ONE line that carries all three."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NCCL_MAX_NCHANNELS")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dry-run-cpu", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dry-run-cpu", "--full", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["dp_path_n1"]["rccl_ranks"] == 1 and out["dp_path_n1"]["ms_per_step"] > 0
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--sweep-channels", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run-cpu", "--full", "--sweep-channels", "--steps", "2",
                         "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -325,6 +325,24 @@ def test_bench_dry_run_n1_runs_the_data_parallel_path_and_the_channel_sweep_rela
     assert [e["NCCL_MAX_NCHANNELS"] for e in sw] == ["default", "8", "16"] and all("error" not in e and e["ms_per_step"] > 0 for e in sw), sw
     assert out["n_gpus"] == 2 and out["comm"]["NCCL_MAX_NCHANNELS"] is None
 
+
+def test_bench_plain_run_times_the_steps_and_prints_the_record_alone():
+    """Without --full the run is set-up, warm-up, the K timed steps and ONE line: no one-rank data-parallel leg, no three-ways
+    comparison (those are --full's), and `steps` / `ms_per_step` are the timed steps'."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    for gpus in ("1", "2"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", gpus, "--dry-run-cpu", "--steps", "3", "--warmup", "1"],
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["n_gpus"] == int(gpus) and out["steps"] == 3 and out["ms_per_step"] > 0 and out["dp_path_n1"] is None
+        assert (out["comm"] or {}).get("ways_ms") is None
 
 def test_wgrad_queue_flushed_is_a_prefix_not_a_count():
     """WgradQueue.flushed releases gradient ranges to the all-reduce: it must be the longest issued PREFIX of the pushed layers

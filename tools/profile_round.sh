@@ -1,15 +1,16 @@
 #!/bin/bash
 # Everything profiles/ needs for one round, run on the GPU box:  tools/profile_round.sh <tag>
-#  1. rocprofv3 --kernel-trace --stats of the default bench.py command (+ its JSON line)
+#  1. rocprofv3 --kernel-trace --stats of the bench.py --full command (+ its JSON line)
 #  2. the same over 10 bare training steps (per-kernel ms/step), and over cfg 3 at B=32
 #  3. PMC passes (separate runs, never combined with trace domains other than --kernel-trace): HBM traffic (FETCH_SIZE /
 #     WRITE_SIZE) of the dominant kernels on their cfg-2 shapes and the SQ / TCC sets of tools/pmc.sh
 tag=${1:-r05}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $OUT
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -f csv -d /tmp/prof_b -o b -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_stdout.txt 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats -f csv -d /tmp/prof_b -o b -- python $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_stdout.txt 2>/dev/null
 cp /tmp/prof_b/*kernel_stats.csv $OUT/bench_kernel_stats.csv
 tail -1 $OUT/bench_stdout.txt > $OUT/bench_under_rocprof.json
 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d /tmp/prof_t -o t -- python $GRAFT_REPO_ROOT/tools/train_steps.py 10 > /dev/null 2>&1
@@ -27,9 +28,9 @@ for cfg in "pw 128 8 512 512 bf16" "pw 128 32 128 128 bf16" "wgradq 128 0 0 0 bf
   name=$(echo $cfg | tr ' ' '_')
   timeout 400 bash tools/pmc.sh ${tag}_$name $cfg > $OUT/pmc_sq_$name.txt 2>&1
 done
-python bench.py > $OUT/bench.json 2> /dev/null
-python bench.py --cfg 3 --batch 32 --graph 1 --no-extras > $OUT/bench_cfg3_b32_graph.json 2> /dev/null
-python bench.py --cfg 3 --batch 32 --graph 0 --no-extras > $OUT/bench_cfg3_b32_eager.json 2> /dev/null
+python bench.py --full > $OUT/bench.json 2> /dev/null
+python bench.py --full --cfg 3 --batch 32 --graph 1 --no-extras > $OUT/bench_cfg3_b32_graph.json 2> /dev/null
+python bench.py --full --cfg 3 --batch 32 --graph 0 --no-extras > $OUT/bench_cfg3_b32_eager.json 2> /dev/null
 # the RCCL path on one rank (init, broadcast, bucketed all-reduce on RCCL's stream, barrier-bracketed timing), eager and as the segmented graph
-for g in 0 1; do MI_BENCH_FORCE_DIST=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2951$g bench.py --gpus 1 --steps 30 --warmup 5 --no-extras --graph $g 2> /dev/null | tail -1 > $OUT/bench_rccl1_graph$g.json; done
+for g in 0 1; do MI_BENCH_FORCE_DIST=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 2951$g bench.py --full --gpus 1 --steps 30 --warmup 5 --no-extras --graph $g 2> /dev/null | tail -1 > $OUT/bench_rccl1_graph$g.json; done
 ls -la $OUT
