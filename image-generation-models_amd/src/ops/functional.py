@@ -1755,3 +1755,133 @@ def conv3x3_uses_splitk(N, H, W, K, Nc, K1=None):
     dc = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=0, w_kn=0,
                     mode=MODE_BF16, K1=K1 or K, ldx=4, ldx2=4, ldy=Nc, ldr=0, accumulate=0)
     return bool(load_library().mi_conv3x3_bf16w_uses_splitk(C.byref(dc)))
+
+
+# ---------------------------------------------------------------------------------------------------------- PixelCNN (csrc/pixelcnn.hip)
+PCNN_PLAIN, PCNN_GATE_TS, PCNN_GATE_TT, PCNN_ELU_GRAD = 0, 1, 2, 3
+
+
+def _ld(t):
+    """pixel pitch of an NHWC activation (a channel slice of a contiguous tensor is legal)"""
+    if t.is_contiguous():                      # size-1 dimensions may carry any stride
+        return t.shape[3]
+    assert t.dim() == 4 and t.stride(3) == 1 and t.stride(1) == t.shape[2] * t.stride(2) and t.stride(0) == t.shape[1] * t.stride(1), \
+        "NHWC activation with dense pixels expected"
+    return t.stride(2)
+
+
+def pcnn_desc(N, H, W, Cin, ldx, Cout, taps, w_strides, C2=0, ldx2=0, w2_strides=(0, 0), epi=PCNN_PLAIN, elu_in=False, accumulate=False,
+              gate_C=0, ldy=0, ldpre=0, ldcond=0, ldr=0, ldaux=0, mode=MODE_FP32):
+    """taps: [(dy, dx, tap index into the weight)]; w_strides = (w_sk, w_sc) -- see mi_pcnn_conv in include/mi_ddpm.h."""
+    from .lib import MiPcnnConvDesc
+    d = MiPcnnConvDesc(N=N, H=H, W=W, Cin=Cin, ldx=ldx, Cout=Cout, ldy=ldy, ntaps=len(taps), w_sk=w_strides[0], w_sc=w_strides[1],
+                       C2=C2, ldx2=ldx2, w2_sk=w2_strides[0], w2_sc=w2_strides[1], epi=epi, elu_in=int(elu_in), accumulate=int(accumulate),
+                       gate_C=gate_C, ldpre=ldpre, ldcond=ldcond, ldr=ldr, ldaux=ldaux, mode=mode)
+    for i, (a, b, t) in enumerate(taps):
+        d.tap_dy[i], d.tap_dx[i], d.tap_w[i] = a, b, t
+    return d
+
+
+def pcnn_conv(x, w, taps, w_strides, Cout, bias=None, x2=None, w2=None, w2_strides=(0, 0), bias2=None, epi=PCNN_PLAIN, cond=None,
+              res=None, aux=None, out=None, pre=None, accumulate=False, elu_in=False, mode=MODE_FP32):
+    """Masked dilated conv over the live taps (mi_pcnn_conv); mode MODE_FP32 / MODE_BF16 (matrix-core operands).  x [N,H,W,Cin] NHWC; gated epilogues return (y [.., Cout/2], pre [.., Cout])."""
+    _need_gpu(x)
+    N, H, W, Cin = x.shape
+    gated = epi in (PCNN_GATE_TS, PCNN_GATE_TT)
+    gC = Cout // 2 if gated else 0
+    if out is None:
+        out = torch.empty((N, H, W, gC if gated else Cout), device=x.device)
+    if gated and pre is None:
+        pre = torch.empty((N, H, W, Cout), device=x.device)
+    d = pcnn_desc(N, H, W, Cin, _ld(x), Cout, taps, w_strides, C2=0 if x2 is None else x2.shape[3], ldx2=0 if x2 is None else _ld(x2),
+                  w2_strides=w2_strides, epi=epi, elu_in=elu_in, accumulate=accumulate, gate_C=gC, ldy=_ld(out),
+                  ldpre=0 if pre is None else _ld(pre), ldcond=0 if cond is None else cond.stride(0), ldr=0 if res is None else _ld(res),
+                  ldaux=0 if aux is None else _ld(aux), mode=mode)
+    check(load_library().mi_pcnn_conv(C.byref(d), _p(x), _p(w), _p(bias), _p(x2), _p(w2), _p(bias2), _p(cond), _p(res), _p(aux), _p(out),
+                                       _p(pre), _stream()), "mi_pcnn_conv")
+    return (out, pre) if gated else out
+
+
+def pcnn_wgrad(x, dy, dw, taps, w_strides, elu_in=False, mode=MODE_FP32):
+    """dw[c*w_sk + o*w_sc + tap] += sum_p x[p + off][c] dy[p][o] over the live taps (mi_pcnn_wgrad); dw flat fp32 storage."""
+    _need_gpu(x)
+    N, H, W, Cin = x.shape
+    d = pcnn_desc(N, H, W, Cin, _ld(x), dy.shape[3], taps, w_strides, elu_in=elu_in, mode=mode)
+    check(load_library().mi_pcnn_wgrad(C.byref(d), _p(x), _p(dy), _ld(dy), _p(dw), _stream()), "mi_pcnn_wgrad")
+
+
+def pcnn_colsum(g, out, out2=None):
+    M = g.shape[0] * g.shape[1] * g.shape[2]
+    check(load_library().mi_pcnn_colsum(M, g.shape[3], _p(g), _ld(g), _p(out), _p(out2), _stream()), "mi_pcnn_colsum")
+
+
+def pcnn_gate_bwd(pre, dout, kind, cond=None, dcond=None, dpre=None):
+    """d pre of a gate (mi_pcnn_gate_bwd); cond / dcond: [N, >= 2C] row views (dcond accumulated)."""
+    N, H, W, C2 = pre.shape
+    Cg = C2 // 2
+    if dpre is None:
+        dpre = torch.empty_like(pre)
+    ldc = cond.stride(0) if cond is not None else (dcond.stride(0) if dcond is not None else 0)
+    if cond is not None and dcond is not None:
+        assert cond.stride(0) == dcond.stride(0)
+    check(load_library().mi_pcnn_gate_bwd(N, H * W, Cg, kind, _p(pre), _ld(pre), _p(cond), ldc, _p(dout), _ld(dout), _p(dpre), _ld(dpre),
+                                           _p(dcond), _stream()), "mi_pcnn_gate_bwd")
+    return dpre
+
+
+def pcnn_small_mm(I, J, Kd, A, sai, sak, B, sbk, sbj, out, ldo, accumulate=False):
+    check(load_library().mi_pcnn_small_mm(I, J, Kd, _p(A), sai, sak, _p(B), sbk, sbj, _p(out), ldo, int(accumulate), _stream()),
+          "mi_pcnn_small_mm")
+
+
+def pcnn_cond_rows(labels, w, out):
+    """out[n][j] = w[j][labels[n]] (mi_pcnn_cond_rows); labels int64 [N], w [J, ncls]."""
+    J, ncls = w.shape
+    check(load_library().mi_pcnn_cond_rows(labels.shape[0], J, ncls, _p(labels), _p(w), _p(out), out.stride(0), _stream()), "mi_pcnn_cond_rows")
+    return out
+
+
+def pcnn_cond_wgrad(labels, dcond, dw):
+    """dw[j][labels[n]] += dcond[n][j] (mi_pcnn_cond_wgrad)."""
+    J, ncls = dw.shape
+    check(load_library().mi_pcnn_cond_wgrad(labels.shape[0], J, ncls, _p(labels), _p(dcond), dcond.stride(0), _p(dw), _stream()),
+          "mi_pcnn_cond_wgrad")
+
+
+def pcnn_head_fwd(h, w, b, img, normalize, lse=None, partial=None, loss=None):
+    """Fused ELU -> 1x1 -> log-sum-exp -> NLL -> bits per dim (mi_pcnn_head_fwd).  Returns (loss [1], lse)."""
+    _need_gpu(h)
+    N, H, W, Ch = h.shape
+    Cc = img.shape[1]
+    lib = load_library()
+    if lse is None:
+        lse = torch.empty(N * H * W * Cc, device=h.device)
+    if partial is None:
+        partial = torch.empty(lib.mi_pcnn_head_partials(N, H * W, Cc), device=h.device)
+    if loss is None:
+        loss = torch.empty(1, device=h.device)
+    check(lib.mi_pcnn_head_fwd(N, Cc, H * W, Ch, _p(h), _ld(h), _p(w), _p(b), _p(img), int(normalize), _p(lse), _p(partial), _p(loss),
+                               _stream()), "mi_pcnn_head_fwd")
+    return loss, lse
+
+
+def pcnn_head_dlogits(h, w, b, img, normalize, lse, gscale=None, out=None):
+    """dlogits [N,H,W,256*Cc] = (softmax - onehot) * (*gscale) / (N*C*H*W*ln 2) (mi_pcnn_head_dlogits)."""
+    N, H, W, Ch = h.shape
+    Cc = img.shape[1]
+    if out is None:
+        out = torch.empty((N, H, W, 256 * Cc), device=h.device)
+    check(load_library().mi_pcnn_head_dlogits(N, Cc, H * W, Ch, _p(h), _ld(h), _p(w), _p(b), _p(img), int(normalize), _p(lse), _p(gscale),
+                                               _p(out), _stream()), "mi_pcnn_head_dlogits")
+    return out
+
+
+def pcnn_sample_step(h, w, b, counter, uniforms, img, xin, normalize):
+    """One inverse-CDF pixel step at *counter (mi_pcnn_sample_step); img NCHW and xin NHWC are written in place."""
+    N, Cc, H, W = img.shape
+    check(load_library().mi_pcnn_sample_step(N, Cc, H, W, h.shape[3], _p(h), _ld(h), _p(w), _p(b), _p(counter), _p(uniforms), _p(img),
+                                              _p(xin), _ld(xin), int(normalize), _stream()), "mi_pcnn_sample_step")
+
+
+def pcnn_zero(t):
+    check(load_library().mi_pcnn_zero(_p(t), t.numel() * t.element_size(), _stream()), "mi_pcnn_zero")

@@ -36,6 +36,13 @@ class MiRowSum(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("ld", C.c_int), ("pad_", C.c_int)]
 
 
+class MiPcnnConvDesc(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("N", "H", "W", "Cin", "ldx", "Cout", "ldy", "ntaps")]
+                + [(n, C.c_int * 25) for n in ("tap_dy", "tap_dx", "tap_w")]
+                + [(n, C.c_int) for n in ("w_sk", "w_sc", "C2", "ldx2", "w2_sk", "w2_sc", "epi", "elu_in", "accumulate", "gate_C",
+                                          "ldpre", "ldcond", "ldr", "ldaux", "mode")])
+
+
 ROWSUM_MAX = 16
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
@@ -203,6 +210,23 @@ SIGNATURES = {
     "mi_gather_rows": [_I, _I, _P, _P, _P, _P],
     "mi_u8_gather_normalize": [_I, _I, _I, _I, _P, _P, _P, _I, _P, _P],
     "mi_scale_by_device_scalar": [_I, _I, _P, _I, _P, _P],
+    "mi_pcnn_conv_supported": [C.POINTER(MiPcnnConvDesc)],
+    "mi_pcnn_conv": [C.POINTER(MiPcnnConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mi_pcnn_wgrad_supported": [C.POINTER(MiPcnnConvDesc)],
+    "mi_pcnn_wgrad": [C.POINTER(MiPcnnConvDesc), _P, _P, _I, _P, _P],
+    "mi_pcnn_colsum": [_I, _I, _P, _I, _P, _P, _P],
+    "mi_pcnn_gate_bwd_supported": [_I],
+    "mi_pcnn_gate_bwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P],
+    "mi_pcnn_small_mm": [_I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P],
+    "mi_pcnn_cond_rows": [_I, _I, _I, _P, _P, _P, _I, _P],
+    "mi_pcnn_cond_wgrad": [_I, _I, _I, _P, _P, _I, _P, _P],
+    "mi_pcnn_head_supported": [_I, _I],
+    "mi_pcnn_head_partials": [_I, _I, _I],
+    "mi_pcnn_head_fwd": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "mi_pcnn_head_dlogits": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    "mi_pcnn_sample_supported": [_I, _I, _I],
+    "mi_pcnn_sample_step": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "mi_pcnn_zero": [_P, _Z, _P],
 }
 OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_conv3x3_wgrad_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),

@@ -50,7 +50,8 @@ class GraphedTrainStep:
         self.model, self.opt = model, optimizer
         imgs = example_batch[0]
         self.x = imgs.clone()
-        self.rest = tuple(example_batch[1:])
+        # labels ride along in static buffers too (the class-conditional PixelCNN reads them inside the step)
+        self.rest = tuple(r.clone() if torch.is_tensor(r) else r for r in example_batch[1:])
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):                               # warm-up outside capture: workspaces, lazy state, autograd buffers
@@ -68,6 +69,9 @@ class GraphedTrainStep:
 
     def __call__(self, batch):
         self.x.copy_(batch[0], non_blocking=True)
+        for dst, src in zip(self.rest, batch[1:]):
+            if torch.is_tensor(dst) and torch.is_tensor(src) and dst.shape == src.shape:
+                dst.copy_(src, non_blocking=True)
         self.graph.replay()
         # the replayed Adam rewrote the flat parameter buffers behind Python's back: anything derived from them that is built
         # OUTSIDE the graph (an eager forward's bf16 weight copies, the sampler's time-bias table) must see a new version

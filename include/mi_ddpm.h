@@ -666,6 +666,77 @@ int mi_gather_rows(int B, int C, const float* table, const int64_t* idx, float* 
 /* x[m*ld + c] *= *scalar (scalar lives on the device: autograd's incoming d(loss), no host sync) */
 int mi_scale_by_device_scalar(int M, int C, float* x, int ld, const float* scalar, void* stream);
 
+/* ---- PixelCNN operators (reference src/models/pixelcnn.py; csrc/pixelcnn.hip) ------------------------------------------------
+ * Masked dilated convolution as an implicit GEMM over the LIVE taps only (masked taps are never read): output pixel (y, x) of
+ * column o = sum over taps t and source channels c of x[y + tap_dy[t]][x + tap_dx[t]][c] * w[c*w_sk + o*w_sc + tap_w[t]]
+ * (zero outside the image), plus, when C2 > 0, sum over c2 of x2[y][x][c2] * w2[c2*w2_sk + o*w2_sc] (the 1x1 conv1x1_1 of the
+ * horizontal stack folded into the same contraction), plus bias[o] + bias2[o] (nullable).  Forward: w_sk = KH*KW, w_sc = Cin*KH*KW
+ * on a PyTorch [Cout][Cin][KH][KW] weight; data gradient: the same call with the strides swapped and the offsets negated.
+ * elu_in: the x operand goes through ELU on load (the output head).  Epilogues:
+ *   MI_PCNN_EPI_PLAIN    y[p][o] = r (+ res[p][o]) (+ y[p][o] when accumulate)
+ *   MI_PCNN_EPI_GATE_TS  Cout = 2 gate_C: pre[p][o] = r (raw), y[p][c] = tanh(r_c + cond[n][c]) * sigmoid(r_{C+c} + cond[n][C+c])
+ *   MI_PCNN_EPI_GATE_TT  the same with tanh * tanh (the horizontal stack); cond (per-sample bias, row stride ldcond) nullable
+ *   MI_PCNN_EPI_ELU_GRAD y[p][o] = (r + res) * elu'(aux[p][o])
+ * Both GEMMs run on the matrix cores (desc mode).  The head and the sampling step stay fp32 in both modes (their softmax / log-sum-exp).
+ * mi_pcnn_head_supported: Cc 1..4 and the head's LDS staging within 64 KB (Ch <= 254).
+ * mi_pcnn_wgrad: dw[c*w_sk + o*w_sc + tap_w[t]] += sum_p x[p + off_t][c] * dy[p][o] (Cin rows, Cout columns; atomics: zero dw first).
+ * mi_pcnn_colsum: out[o] (and out2[o], nullable) += sum of column o of g [M][C] (bias gradients; atomics).
+ * mi_pcnn_gate_bwd: kind = MI_PCNN_EPI_GATE_TS / _TT; d pre [N*HW][2C] from the raw pre-activations (+ cond) and d out [N*HW][C];
+ *   dcond (nullable, row stride ldcond) += per-(sample, channel) sums of d pre (atomics).
+ * mi_pcnn_small_mm: out[i][j] (+)= sum_k A[i*sai + k*sak] B[k*sbk + j*sbj] (conditioning biases and their weight gradient).
+ * mi_pcnn_head_fwd: ELU(h) -> 1x1 to 256*Cc logits (w [256*Cc][Ch], class k of colour col is column k*Cc + col) -> log-sum-exp ->
+ *   NLL at the reference's truncated target of img (NCHW, fp32) -> lse[N*HW*Cc], partial[mi_pcnn_head_partials], and
+ *   *loss = mean bits per dim.  The logits are not written.
+ * mi_pcnn_head_dlogits: dl[p][k*Cc + col] = (softmax - onehot) * (*gscale, nullable = 1) / (N*Cc*HW*ln 2), recomputed from lse.
+ * mi_pcnn_sample_step: at pixel *counter (raster order over H*W) pick, for every (sample, colour), k = min{k : cdf_k > u} under the
+ *   fp32 softmax of its 256 logits (clamped to 255; u = uniforms[pixel][n*Cc + col]) and write k/255 (2k/255 - 1 when normalize)
+ *   into img (NCHW) and xin (NHWC, pixel pitch ldx) -- unless no sample has -1 at that pixel; then *counter += 1.  One workgroup.
+ * mi_pcnn_zero: zero fill on the stream (a kernel node under graph capture). */
+#define MI_PCNN_MAX_TAPS 25
+#define MI_PCNN_EPI_PLAIN 0
+#define MI_PCNN_EPI_GATE_TS 1
+#define MI_PCNN_EPI_GATE_TT 2
+#define MI_PCNN_EPI_ELU_GRAD 3
+#define MI_PCNN_MODE_FP32 0
+#define MI_PCNN_MODE_BF16 1
+typedef struct MiPcnnConvDesc {
+    int N, H, W;
+    int Cin, ldx;             /* channels of the tapped source (contraction rows per tap) and its pixel pitch */
+    int Cout, ldy;            /* GEMM columns and the pixel pitch of y (gated: of the gated output) */
+    int ntaps;
+    int tap_dy[MI_PCNN_MAX_TAPS], tap_dx[MI_PCNN_MAX_TAPS], tap_w[MI_PCNN_MAX_TAPS];
+    int w_sk, w_sc;
+    int C2, ldx2, w2_sk, w2_sc;
+    int epi, elu_in, accumulate, gate_C;
+    int ldpre, ldcond, ldr, ldaux;
+    int mode;                 /* MI_PCNN_MODE_FP32: fp32-exact MFMA; MI_PCNN_MODE_BF16: bf16 operands, fp32 accumulate */
+} MiPcnnConvDesc;
+int mi_pcnn_conv_supported(const MiPcnnConvDesc* d);
+int mi_pcnn_conv(const MiPcnnConvDesc* d, const float* x, const float* w, const float* bias, const float* x2, const float* w2,
+                 const float* bias2, const float* cond, const float* res, const float* aux, float* y, float* pre, void* stream);
+int mi_pcnn_wgrad_supported(const MiPcnnConvDesc* d);
+int mi_pcnn_wgrad(const MiPcnnConvDesc* d, const float* x, const float* dy, int lddy, float* dw, void* stream);
+int mi_pcnn_colsum(int M, int C, const float* g, int ld, float* out, float* out2, void* stream);
+int mi_pcnn_gate_bwd_supported(int C);
+int mi_pcnn_gate_bwd(int N, int HW, int C, int kind, const float* pre, int ldpre, const float* cond, int ldcond, const float* dout,
+                     int ldo, float* dpre, int lddp, float* dcond, void* stream);
+int mi_pcnn_small_mm(int I, int J, int Kd, const float* A, int sai, int sak, const float* B, int sbk, int sbj, float* out, int ldo,
+                     int accumulate, void* stream);
+/* conditioning from int64 labels (out-of-range labels contribute nothing): out[n][j] = w[j][labels[n]];
+ * dw[j][labels[n]] += dcond[n][j] (atomics).  w: the cond_proj weights as one [J][ncls] matrix. */
+int mi_pcnn_cond_rows(int N, int J, int ncls, const int64_t* labels, const float* w, float* out, int ldo, void* stream);
+int mi_pcnn_cond_wgrad(int N, int J, int ncls, const int64_t* labels, const float* dcond, int ldd, float* dw, void* stream);
+int mi_pcnn_head_supported(int Cc, int Ch);
+int mi_pcnn_head_partials(int N, int HW, int Cc);
+int mi_pcnn_head_fwd(int N, int Cc, int HW, int Ch, const float* h, int ldh, const float* w, const float* b, const float* img,
+                     int normalize, float* lse, float* partial, float* loss, void* stream);
+int mi_pcnn_head_dlogits(int N, int Cc, int HW, int Ch, const float* h, int ldh, const float* w, const float* b, const float* img,
+                         int normalize, const float* lse, const float* gscale, float* dl, void* stream);
+int mi_pcnn_sample_supported(int N, int Cc, int Ch);
+int mi_pcnn_sample_step(int N, int Cc, int H, int W, int Ch, const float* h, int ldh, const float* w, const float* b, int* counter,
+                        const float* uniforms, float* img, float* xin, int ldx, int normalize, void* stream);
+int mi_pcnn_zero(void* p, size_t bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,116 @@
+"""PixelCNN host layer without a GPU: config composition, state_dict contract and seeded init against the reference's fixture."""
+import hashlib
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "image-generation-models_amd")
+
+
+def _dm(ch, H, W, normalize=False):
+    return types.SimpleNamespace(width=W, height=H, channels=ch, transforms=types.SimpleNamespace(normalize=normalize))
+
+
+@pytest.fixture(scope="module")
+def kats(golden_dir):
+    return np.load(os.path.join(golden_dir, "pixelcnn_kats.npz"))
+
+
+@pytest.mark.parametrize("exp,ch,hw", [("mnist", 1, 28), ("cifar10", 3, 32), ("celeba", 3, 64), ("synthetic", 1, 28)])
+def test_pixelcnn_experiments_compose(exp, ch, hw):
+    from src.runtime.config import Composer
+    c = Composer(os.path.join(PKG, "configs")).compose("config", [f"experiment=pixelcnn/{exp}"])
+    assert c.model._target_ == "src.models.pixelcnn.PixelCNN"
+    assert c.model.hidden_dim == 64 and float(c.model.lr) == 1e-3 and c.model.class_condition is False
+    assert c.model.n_classes == c.datamodule.n_classes
+    assert c.datamodule.channels == ch and c.datamodule.width == hw
+    assert c.datamodule.transforms.normalize is False
+    assert "sample" in c.callbacks and "tqdm" in c.callbacks
+
+
+@pytest.mark.parametrize("tag,ch,hw,ncls", [("64", 1, 28, None), ("64c", 3, 32, 10)])
+def test_pixelcnn_state_dict_keys_order_shapes(kats, tag, ch, hw, ncls):
+    from src.models.pixelcnn import PixelCNN
+    m = PixelCNN(_dm(ch, hw, hw), 64, class_condition=ncls is not None, n_classes=ncls)
+    sd = m.state_dict()
+    assert list(sd.keys()) == [str(k) for k in kats["keys" + tag]]
+    for v, s in zip(sd.values(), kats["shapes" + tag]):
+        assert list(v.shape) == [int(d) for d in s if d >= 0]
+
+
+def test_pixelcnn_seeded_init_matches_reference_sha(kats):
+    from src.models.pixelcnn import PixelCNN
+    torch.manual_seed(0)
+    sd = PixelCNN(_dm(1, 28, 28), 64).state_dict()
+    h = hashlib.sha256()
+    for k, v in sd.items():
+        h.update(k.encode())
+        h.update(v.detach().contiguous().numpy().astype(np.float32).tobytes())
+    assert h.hexdigest() == str(kats["sha64"])
+
+
+def test_pixelcnn_parameters_are_views_of_one_flat_buffer():
+    from src.models.pixelcnn import PixelCNN
+    m = PixelCNN(_dm(3, 8, 8), 8, class_condition=True, n_classes=10)
+    base = m.flat_params.data_ptr()
+    end = base + m.flat_params.numel() * 4
+    for p in m.parameters():
+        assert base <= p.data_ptr() < end
+    n = sum(p.numel() for p in m.parameters())
+    assert n <= m.flat_params.numel() < n + 64
+
+
+@pytest.mark.parametrize("hidden,ch", [(12, 1), (0, 1), (64, 5), (256, 1)])
+def test_pixelcnn_unsupported_shapes_raise(hidden, ch):
+    from src.models.pixelcnn import PixelCNN
+    with pytest.raises(ValueError, match="not supported"):
+        PixelCNN(_dm(ch, 8, 8), hidden)
+
+
+def test_pixelcnn_live_taps_follow_the_reference_masks():
+    from src.models.pixelcnn import horizontal_mask, live_taps, vertical_mask
+    assert len(live_taps(vertical_mask(3))) == 6 and len(live_taps(horizontal_mask(3))) == 2
+    assert len(live_taps(vertical_mask(5, True))) == 10 and len(live_taps(horizontal_mask(5, True))) == 2
+    # dilation 4, 3x3 vertical: rows -4 and 0, columns -4, 0, 4 (padding dilation * (k - 1) // 2)
+    assert sorted((a, b) for a, b, _ in live_taps(vertical_mask(3), 4)) == [(-4, -4), (-4, 0), (-4, 4), (0, -4), (0, 0), (0, 4)]
+    assert sorted((a, b) for a, b, _ in live_taps(horizontal_mask(5, True))) == [(0, -2), (0, -1)]
+
+
+def test_pixelcnn_abi_symbols_declared_bound_exported():
+    import re
+    import subprocess
+    from src.ops.lib import SIGNATURES, library_path, load_library
+    hdr = open(os.path.join(ROOT, "include", "mi_ddpm.h")).read()
+    names = set(re.findall(r"\b(mi_pcnn_[a-z0-9_]+)\s*\(", hdr))
+    assert {"mi_pcnn_conv", "mi_pcnn_wgrad", "mi_pcnn_gate_bwd", "mi_pcnn_head_fwd", "mi_pcnn_head_dlogits", "mi_pcnn_sample_step",
+            "mi_pcnn_conv_supported", "mi_pcnn_head_supported", "mi_pcnn_sample_supported", "mi_pcnn_gate_bwd_supported"} <= names
+    assert names <= set(SIGNATURES)
+    lib = load_library()
+    assert lib.mi_abi_version() == 4
+    out = subprocess.run(["nm", "-D", "--defined-only", library_path()], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()}
+    assert names <= exported
+    assert lib.mi_pcnn_head_supported(3, 64) == 1 and lib.mi_pcnn_head_supported(5, 64) == 0
+
+
+def test_pixelcnn_oracle_reproduces_the_fixture(kats):
+    """The CPU restatement the GPU tests compare against gives the reference's logits and bpd."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _pixelcnn_oracle as O
+    for tag, norm in (("u", False), ("c", True)):
+        p = {k[len(tag) + 5:]: torch.from_numpy(kats[k]) for k in kats.files if k.startswith(tag + ".sd0.")}
+        x = torch.from_numpy(kats[tag + ".x"])
+        oh = None
+        if tag + ".labels" in kats.files:
+            oh = torch.nn.functional.one_hot(torch.from_numpy(kats[tag + ".labels"]), 10).float()
+        lg = O.forward(p, x, oh)
+        pos = kats[tag + ".pos"]
+        got = lg[pos[:, 0], :, pos[:, 1], pos[:, 2], pos[:, 3]]
+        ref = torch.from_numpy(kats[tag + ".logits"])
+        assert float((got - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
+        assert abs(float(O.bpd(p, x, oh, norm)) - float(kats[tag + ".bpd"])) <= 1e-5 * float(kats[tag + ".bpd"])

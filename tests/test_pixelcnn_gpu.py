@@ -1,0 +1,427 @@
+"""PixelCNN on the MI355X: the masked-conv / gate / head / sampling kernels against torch on the CPU, the tiny nets against the
+reference's fixture (tests/golden/pixelcnn_kats.npz), causality, the replayed sampler, and run.py end to end."""
+import json
+import math
+import os
+import sys
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _pixelcnn_oracle as O  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "image-generation-models_amd")
+
+
+def _K():
+    from src.ops import functional as K
+    return K
+
+
+def _dm(ch, H, W, normalize=False):
+    return types.SimpleNamespace(width=W, height=H, channels=ch, transforms=types.SimpleNamespace(normalize=normalize))
+
+
+def _rel(a, b):
+    return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max()) / max(float(b.abs().max()), 1e-30)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous().to(DEV)
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2).cpu()
+
+
+# ------------------------------------------------------------------ 1. masked conv: forward, data gradient, weight gradient
+CONVS = [("v", 3, 1, False), ("v", 3, 2, False), ("v", 3, 4, False), ("h", 3, 1, False), ("h", 3, 4, False), ("v", 5, 1, True),
+         ("h", 5, 1, True)]
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+@pytest.mark.parametrize("kind,k,dil,mc", CONVS)
+@pytest.mark.parametrize("cin,hw,n", [(1, (28, 28), 2), (3, (32, 32), 2), (8, (7, 5), 3), (64, (64, 64), 1)])
+def test_masked_conv_fwd_dgrad_wgrad(kind, k, dil, mc, cin, hw, n, mode):
+    """fp32 mode: fp32-exact MFMA, <= 1e-5 of max |ref|.  bf16 mode: operands rounded to bf16 (2^-9 relative each) and fp32
+    accumulation: <= 2e-2 of max |ref| against the fp32 reference."""
+    from src.models.pixelcnn import horizontal_mask, live_taps, vertical_mask
+    K = _K()
+    H, W = hw
+    cout = 16 if cin < 64 else 128
+    mask = vertical_mask(k, mc) if kind == "v" else horizontal_mask(k, mc)
+    kh, kw = mask.shape
+    T = kh * kw
+    taps = live_taps(mask, dil)
+    w = torch.randn(cout, cin, kh, kw) * 0.2
+    wm = w * mask
+    b = torch.randn(cout)
+    x = torch.randn(n, cin, H, W, requires_grad=True)
+    pad = (dil * (kh - 1) // 2, dil * (kw - 1) // 2)
+    ref = F.conv2d(x, wm.requires_grad_(), b, padding=pad, dilation=dil)
+    dy = torch.randn_like(ref)
+    ref.backward(dy)
+    wd = w.to(DEV)
+    md, tol = (K.MODE_FP32, 1e-5) if mode == "fp32" else (K.MODE_BF16, 2e-2)
+    y = K.pcnn_conv(_nhwc(x.detach()), wd, taps, (T, cin * T), cout, bias=b.to(DEV), mode=md)
+    assert _rel(_nchw(y), ref) <= tol
+    dx = K.pcnn_conv(_nhwc(dy), wd, [(-a, -c, t) for a, c, t in taps], (cin * T, T), cin, mode=md)
+    assert _rel(_nchw(dx), x.grad) <= tol
+    dw = torch.zeros_like(wd)
+    K.pcnn_wgrad(_nhwc(x.detach()), _nhwc(dy), dw, taps, (T, cin * T), mode=md)
+    assert _rel(dw.cpu() * mask, wm.grad * mask) <= tol
+    assert float((dw.cpu() * (1 - mask)).abs().max()) == 0.0           # masked taps: never written
+
+
+# ------------------------------------------------------------------ 2. gated epilogue (with the 1x1 second source) and gate backward
+@pytest.mark.parametrize("C,cond", [(8, False), (64, True), (24, True)])
+def test_gated_layer_and_gate_backward(C, cond):
+    K = _K()
+    from src.models.pixelcnn import horizontal_mask, live_taps, vertical_mask
+    n, H, W = 3, 9, 11
+    vx = torch.randn(n, C, H, W)
+    hx = torch.randn(n, C, H, W)
+    Wv, bv = torch.randn(2 * C, C, 3, 3) * 0.2, torch.randn(2 * C) * 0.1
+    Wh, bh = torch.randn(2 * C, C, 1, 3) * 0.2, torch.randn(2 * C) * 0.1
+    W11, b11 = torch.randn(2 * C, 2 * C, 1, 1) * 0.1, torch.randn(2 * C) * 0.1
+    cb = torch.randn(n, 4 * C) * 0.5 if cond else None
+    vm, hm = vertical_mask(3), horizontal_mask(3)
+    leaves = [t.requires_grad_() for t in (Wv, bv, Wh, bh, W11)]
+    cbr = cb.clone().requires_grad_() if cond else None
+    vc = F.conv2d(vx, Wv * vm, bv, padding=2, dilation=2)
+    v1, v2 = vc.chunk(2, 1)
+    hc = F.conv2d(hx, Wh * hm, bh, padding=(0, 2), dilation=2) + F.conv2d(vc, W11, b11)
+    h1, h2 = hc.chunk(2, 1)
+    if cond:
+        v1, v2 = v1 + cbr[:, :C, None, None], v2 + cbr[:, C:2 * C, None, None]
+        h1, h2 = h1 + cbr[:, 2 * C:3 * C, None, None], h2 + cbr[:, 3 * C:, None, None]
+    vout, gh = torch.tanh(v1) * torch.sigmoid(v2), torch.tanh(h1) * torch.tanh(h2)
+    dv, dg = torch.randn_like(vout), torch.randn_like(gh)
+    condd = cb.to(DEV) if cond else None
+    g_out, vpre = K.pcnn_conv(_nhwc(vx), Wv.detach().to(DEV), live_taps(vm, 2), (9, 9 * C), 2 * C, bias=bv.detach().to(DEV),
+                              epi=K.PCNN_GATE_TS, cond=None if condd is None else condd[:, :2 * C])
+    assert _rel(_nchw(g_out), vout) <= 1e-5 and _rel(_nchw(vpre), vc) <= 1e-5
+    g_h, hpre = K.pcnn_conv(_nhwc(hx), Wh.detach().to(DEV), live_taps(hm, 2), (3, 3 * C), 2 * C, bias=bh.detach().to(DEV), x2=vpre,
+                            w2=W11.detach().to(DEV), w2_strides=(1, 2 * C), bias2=b11.detach().to(DEV), epi=K.PCNN_GATE_TT,
+                            cond=None if condd is None else condd[:, 2 * C:])
+    assert _rel(_nchw(g_h), gh) <= 1e-5 and _rel(_nchw(hpre), hc) <= 1e-5
+    # gate backward against autograd through the gates alone
+    (vout * dv).sum().add((gh * dg).sum()).backward()
+    pv = vc.detach().requires_grad_()
+    ph = hc.detach().requires_grad_()
+    a1, a2 = pv.chunk(2, 1)
+    c1, c2 = ph.chunk(2, 1)
+    cbr2 = cb.clone().requires_grad_() if cond else None
+    if cond:
+        a1, a2 = a1 + cbr2[:, :C, None, None], a2 + cbr2[:, C:2 * C, None, None]
+        c1, c2 = c1 + cbr2[:, 2 * C:3 * C, None, None], c2 + cbr2[:, 3 * C:, None, None]
+    ((torch.tanh(a1) * torch.sigmoid(a2) * dv).sum() + (torch.tanh(c1) * torch.tanh(c2) * dg).sum()).backward()
+    dcond = torch.zeros(n, 4 * C, device=DEV) if cond else None
+    dvp = K.pcnn_gate_bwd(vpre, _nhwc(dv), K.PCNN_GATE_TS, cond=None if condd is None else condd[:, :2 * C],
+                          dcond=None if dcond is None else dcond[:, :2 * C])
+    dhp = K.pcnn_gate_bwd(hpre, _nhwc(dg), K.PCNN_GATE_TT, cond=None if condd is None else condd[:, 2 * C:],
+                          dcond=None if dcond is None else dcond[:, 2 * C:])
+    assert _rel(_nchw(dvp), pv.grad) <= 1e-5 and _rel(_nchw(dhp), ph.grad) <= 1e-5
+    if cond:
+        assert _rel(dcond, cbr2.grad) <= 1e-5
+        # the cond_proj weight gradient: d W[j][k] = sum_n dcond[n][j] onehot[n][k]
+        lab = torch.tensor([1, 4, 1])
+        oh = F.one_hot(lab, 6).float()
+        gw = torch.zeros(4 * C, 6, device=DEV)
+        K.pcnn_small_mm(4 * C, 6, n, dcond, 1, 4 * C, oh.to(DEV), 6, 1, gw, 6)
+        assert _rel(gw, cbr2.grad.t() @ oh) <= 1e-5
+
+
+# ------------------------------------------------------------------ 3. fused head against F.cross_entropy
+@pytest.mark.parametrize("Cc,normalize", [(1, False), (3, False), (3, True)])
+def test_fused_head_against_cross_entropy(Cc, normalize):
+    K = _K()
+    n, H, W, Ch = 3, 7, 6, 64
+    h = torch.randn(n, Ch, H, W)
+    w = (torch.randn(256 * Cc, Ch, 1, 1) * 0.2).requires_grad_()
+    b = (torch.randn(256 * Cc) * 0.1).requires_grad_()
+    k = torch.randint(0, 256, (n, Cc, H, W))
+    k[0, 0, 0, :3] = torch.tensor([0, 255, 1])
+    if normalize:
+        k[1].view(-1)[:63] = torch.arange(1, 64)                         # the values that truncate one low
+        x = k.float() * 2 / 255 - 1
+    else:
+        x = k.float() / 255
+    hr = h.clone().requires_grad_()
+    logits = F.conv2d(F.elu(hr), w, b)
+    logits = logits.reshape(n, 256, Cc, H, W)
+    tgt = O.target(x, normalize)
+    ref = (F.cross_entropy(logits, tgt, reduction="none").mean([1, 2, 3]) / torch.log(torch.tensor(2.0))).mean()
+    ref.backward()
+    hd, wd, bd, xd = _nhwc(h), w.detach().reshape(256 * Cc, Ch).to(DEV), b.detach().to(DEV), x.to(DEV)
+    loss, lse = K.pcnn_head_fwd(hd, wd, bd, xd, normalize)
+    assert abs(float(loss) - float(ref)) <= 1e-5 * float(ref)
+    g = torch.ones(1, device=DEV)
+    dl = K.pcnn_head_dlogits(hd, wd, bd, xd, normalize, lse, gscale=g)
+    dh = K.pcnn_conv(dl, wd, [(0, 0, 0)], (Ch, 1), Ch, epi=K.PCNN_ELU_GRAD, aux=hd)
+    assert _rel(_nchw(dh), hr.grad) <= 1e-4
+    dw = torch.zeros_like(wd)
+    K.pcnn_wgrad(hd, dl, dw, [(0, 0, 0)], (1, Ch), elu_in=True)
+    assert _rel(dw, w.grad.reshape(256 * Cc, Ch)) <= 1e-4
+    db = torch.zeros_like(bd)
+    K.pcnn_colsum(dl, db)
+    assert _rel(db, b.grad) <= 1e-4
+
+
+# ------------------------------------------------------------------ 4. tiny nets against the reference's fixture
+def _tiny(kats, tag, mode="fp32"):
+    from src.models.pixelcnn import PixelCNN
+    x = torch.from_numpy(kats[tag + ".x"])
+    ncls = 10 if tag + ".labels" in kats.files else None
+    m = PixelCNN(_dm(x.shape[1], x.shape[2], x.shape[3], normalize=tag == "c"), 8, class_condition=ncls is not None, n_classes=ncls)
+    sd = {k[len(tag) + 5:]: torch.from_numpy(kats[k]) for k in kats.files if k.startswith(tag + ".sd0.")}
+    m.load_state_dict(sd)
+    m.compute_mode = mode
+    m.to(DEV)
+    lab = torch.from_numpy(kats[tag + ".labels"]).to(DEV) if ncls else None
+    masks = {k[:-5]: v for k, v in sd.items() if k.endswith(".mask")}
+    return m, x.to(DEV), lab, masks
+
+
+def _mask_for(masks, key):
+    for pre, mk in masks.items():
+        if key == pre + ".conv.weight":
+            return mk
+    return None
+
+
+@pytest.fixture(scope="module")
+def kats(golden_dir):
+    return np.load(os.path.join(golden_dir, "pixelcnn_kats.npz"))
+
+
+@pytest.mark.parametrize("tag", ["u", "c"])
+def test_tiny_net_logits_bpd_gradients(kats, tag):
+    m, x, lab, masks = _tiny(kats, tag)
+    pos = kats[tag + ".pos"]
+    oh = F.one_hot(lab, 10).float() if lab is not None else None
+    logits = m(x, oh).cpu()
+    ref = torch.from_numpy(kats[tag + ".logits"])
+    assert _rel(logits[pos[:, 0], :, pos[:, 1], pos[:, 2], pos[:, 3]], ref) <= 1e-4
+    m.train()
+    bpd = m.calc_likelihood(x, lab)
+    bpd.backward()
+    rb = float(kats[tag + ".bpd"])
+    assert abs(float(bpd) - rb) <= 1e-5 * rb
+    worst = 0.0
+    for k, p in m.named_parameters():
+        r = torch.from_numpy(kats[f"{tag}.grad.{k}"])
+        mk = _mask_for(masks, k)
+        g = p.grad.cpu()
+        if mk is not None:
+            r = r * mk
+            assert float((g * (1 - mk)).abs().max()) == 0.0
+        if float(r.abs().max()) > 0:
+            worst = max(worst, _rel(g, r))
+    assert worst <= 1e-4, worst
+
+
+@pytest.mark.parametrize("tag", ["u", "c"])
+def test_tiny_net_five_adam_steps(kats, tag):
+    """5 FlatAdam steps in fp32 mode against the reference's torch Adam: per-step bpd <= 1e-4, the parameter vector's norm under
+    the masks after every step <= 1e-5 relative, every tensor's displacement <= 2e-2 rel-L2 under the mask, masked entries exactly 0."""
+    m, x, lab, masks = _tiny(kats, tag)
+    opt = m.configure_optimizers()[0][0]
+    before = {k: v.detach().cpu().clone() for k, v in m.named_parameters()}
+    traj, wn = [], []
+    m.train()
+    for _ in range(5):
+        opt.zero_grad()
+        loss = m.calc_likelihood(x, lab)
+        loss.backward()
+        opt.step()
+        traj.append(float(loss))
+        wn.append(float(m.flat_params.double().norm()))               # masked entries are 0 here: the norm under the masks
+    assert np.abs(np.array(traj) - kats[tag + ".traj_bpd"]).max() <= 1e-4, (traj, kats[tag + ".traj_bpd"])
+    assert np.abs(np.array(wn) / kats[tag + ".traj_wnorm"] - 1).max() <= 1e-5, (wn, kats[tag + ".traj_wnorm"])
+    for k, p in m.named_parameters():
+        mk = _mask_for(masks, k)
+        disp = p.detach().cpu() - before[k]
+        r = torch.from_numpy(kats[f"{tag}.disp.{k}"])
+        if mk is not None:
+            assert float((p.detach().cpu() * (1 - mk)).abs().max()) == 0.0        # masked entries stay exactly 0
+            disp, r = disp * mk, r * mk
+        if float(r.norm()) > 0:
+            assert float((disp - r).norm()) <= 2e-2 * float(r.norm()), k
+        else:
+            assert float(disp.norm()) == 0.0, k
+
+
+@pytest.mark.parametrize("tag", ["u", "c"])
+def test_tiny_net_bf16_within_reference_budget(kats, tag):
+    """bf16 mode: logits within 2x the reference's own CPU bf16-autocast error (fixture), bpd within 1e-2 relative."""
+    m, x, lab, _ = _tiny(kats, tag, mode="bf16")
+    pos = kats[tag + ".pos"]
+    oh = F.one_hot(lab, 10).float() if lab is not None else None
+    logits = m(x, oh).cpu()
+    ref = torch.from_numpy(kats[tag + ".logits"])
+    err = _rel(logits[pos[:, 0], :, pos[:, 1], pos[:, 2], pos[:, 3]], ref)
+    assert err <= 2 * float(kats[tag + ".bf16_err"]), (err, float(kats[tag + ".bf16_err"]))
+    with torch.no_grad():
+        bpd = float(m.calc_likelihood(x, lab))
+    assert abs(bpd - float(kats[tag + ".bpd"])) <= 1e-2 * float(kats[tag + ".bpd"])
+
+
+def test_graphed_conditional_step_reads_each_batch_labels():
+    """The class-conditional step replayed as one hipGraph (what the trainer does from step 2 on) uses the labels of the batch it
+    is given, not those of the batch it was captured on: same images, other labels -> the eager step's loss and weights."""
+    from src.models.pixelcnn import PixelCNN
+    from src.runtime.graphed import GraphedTrainStep
+    from src.runtime.optim import FlatAdam
+    torch.manual_seed(11)
+    ms = [PixelCNN(_dm(3, 8, 8), 16, class_condition=True, n_classes=10) for _ in range(2)]
+    ms[1].load_state_dict(ms[0].state_dict())
+    x = (torch.randint(0, 256, (6, 3, 8, 8)).float() / 255).to(DEV)
+    la, lb = torch.tensor([0, 1, 2, 3, 4, 5], device=DEV), torch.tensor([9, 8, 7, 6, 5, 4], device=DEV)
+    opts = []
+    for i, m in enumerate(ms):
+        m.to(DEV).train()
+        opts.append(FlatAdam(m, lr=1e-3, device_state=(i == 0)))
+        m.training_step((x, la), 0).backward()
+        opts[-1].step()
+    gs = GraphedTrainStep(ms[0], opts[0], (x, la), warmup=0)         # captured on labels la; the capture executes nothing
+    got = float(gs((x, lb)))
+    want = ms[1].training_step((x, lb), 1)
+    want.backward()
+    opts[1].step()
+    assert abs(got - float(want)) <= 1e-5 * abs(float(want)), (got, float(want))
+    assert _rel(ms[0].flat_params, ms[1].flat_params) <= 1e-5
+
+
+# ------------------------------------------------------------------ causality: masked taps are never read
+def test_causality_nan_poisoned_future_pixels():
+    from src.models.pixelcnn import PixelCNN
+    torch.manual_seed(1)
+    m = PixelCNN(_dm(3, 12, 10), 16).to(DEV)
+    x = torch.randint(0, 256, (2, 3, 12, 10), device=DEV).float() / 255
+    base = m(x)
+    for p in (0, 37, 119):
+        xp = x.clone().reshape(2, 3, -1)
+        xp[:, :, p:] = float("nan")
+        out = m(xp.reshape_as(x)).reshape(2, 256, 3, -1)
+        ok = out[..., :p + 1]
+        assert torch.isfinite(ok).all()
+        assert torch.equal(ok, base.reshape(2, 256, 3, -1)[..., :p + 1])
+
+
+# ------------------------------------------------------------------ 5. sampler, teacher-forced against the oracle
+@pytest.mark.parametrize("ch", [1, 3])
+def test_sampler_teacher_forced(ch):
+    from src.models.pixelcnn import PixelCNN
+    torch.manual_seed(2)
+    m = PixelCNN(_dm(ch, 8, 8), 8)
+    # a peaked output distribution, as a trained net has (top class ~0.7-0.9): the CDF boundaries of the near-zero classes then
+    # coincide, so few uniforms fall within the 1e-5 skip band (an untrained net is near uniform: 256 x 2e-5 = 0.5 % of draws)
+    with torch.no_grad():
+        m.conv_out.weight.mul_(40.0)
+        m.conv_out.bias.mul_(40.0)
+    m.to(DEV)
+    N, H, W = 4, 8, 8
+    g = torch.Generator().manual_seed(5)
+    tape = torch.rand(H * W, N * ch, generator=g)
+    m.uniform_source = lambda shape, device: tape.reshape(shape).to(device)
+    rec = []
+    m.sample((N, ch, H, W))                               # capture
+    s = next(iter(m._samplers.values()))
+    s.run(record=rec)
+    p = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+    prev = torch.full((N, ch, H, W), -1.0)
+    skipped = 0
+    for step, img in enumerate(rec):
+        img = img.cpu()
+        hh, ww = divmod(step, W)
+        probs = F.softmax(O.forward(p, prev)[:, :, :, hh, ww].permute(0, 2, 1), -1).reshape(N * ch, 256)
+        k, dist = O.pick(probs, tape[step])
+        want = (k.float() / 255).reshape(N, ch)
+        got = img[:, :, hh, ww]
+        near = dist < 1e-5
+        skipped += int(near.sum())
+        assert torch.equal(got.reshape(-1)[~near], want.reshape(-1)[~near]), step
+        other = img.clone()
+        other[:, :, hh, ww] = prev[:, :, hh, ww]
+        assert torch.equal(other, prev)                   # nothing else changes
+        prev = img
+    draws = len(rec) * N * ch
+    assert skipped * 10000 <= max(draws, 10000), (skipped, draws)      # at most 1 draw in 10 000 (at this size: none expected)
+
+
+# ------------------------------------------------------------------ 6. sampling kernel distribution
+def _sample_fixed(logits, uniforms, N, steps):
+    """Drive mi_pcnn_sample_step with logits = bias (zero weights) over `steps` pixels of an N-sample, 1-channel image."""
+    K = _K()
+    h = torch.zeros(N, 1, steps, 8, device=DEV)
+    w = torch.zeros(256, 8, device=DEV)
+    img = torch.full((N, 1, 1, steps), -1.0, device=DEV)
+    xin = torch.zeros(N, 1, steps, 1, device=DEV)
+    cnt = torch.zeros(1, dtype=torch.int32, device=DEV)
+    for _ in range(steps):
+        K.pcnn_sample_step(h, w, logits.to(DEV), cnt, uniforms.to(DEV), img, xin, False)
+    assert int(cnt) == steps
+    return torch.round(img.cpu().reshape(-1) * 255).long()
+
+
+def test_sampling_kernel_distribution():
+    torch.manual_seed(3)
+    logits = torch.randn(256) * 2
+    N, steps = 4096, 245                                  # 1 003 520 draws
+    u = torch.rand(steps, N)
+    k = _sample_fixed(logits, u, N, steps)
+    prob = F.softmax(logits.double(), 0)
+    cnt = torch.bincount(k, minlength=256).double()
+    n = k.numel()
+    sig = (n * prob * (1 - prob)).sqrt()
+    assert float(((cnt - n * prob).abs() / sig.clamp(min=1e-9)).max()) <= 5.0
+
+
+def test_sampling_kernel_degenerate_cases():
+    N = 64
+    one = torch.full((256,), -1e4)
+    one[77] = 0
+    assert (_sample_fixed(one, torch.rand(2, N), N, 2) == 77).all()
+    uni = torch.zeros(256)
+    u = torch.tensor([[0.0, 1 - 2 ** -24, 0.5, 0.25] * (N // 4)])
+    k = _sample_fixed(uni, u, N, 1)
+    assert k[0] == 0 and k[1] == 255 and k[2] == 128 and k[3] == 64
+
+
+# ------------------------------------------------------------------ 7. completion semantics
+def test_completion_semantics():
+    from src.models.pixelcnn import PixelCNN
+    torch.manual_seed(4)
+    m = PixelCNN(_dm(1, 4, 4), 8).to(DEV)
+    img = (torch.randint(0, 256, (3, 1, 4, 4)).float() / 255).to(DEV)
+    img[1, 0, 2, 1] = -1                                   # only sample 1 misses pixel (2, 1)
+    img[0, 0, 2, 1] = img[2, 0, 2, 1] = 0.3                # given, and off the k / 255 grid: a rewrite is visible
+    out = m.sample((3, 1, 4, 4), img=img.clone())
+    changed = (out != img)
+    changed[:, :, 2, 1] = False
+    assert not changed.any()                              # fully given pixels are untouched
+    col = out[:, 0, 2, 1].cpu()
+    assert (col >= 0).all() and torch.equal(col, torch.round(col * 255) / 255)   # the whole batch is rewritten with draws
+
+
+# ------------------------------------------------------------------ 8. run.py end to end
+@pytest.mark.parametrize("cond", [False, True])
+def test_run_py_pixelcnn_end_to_end(tmp_path, cond):
+    import subprocess
+    cmd = [sys.executable, os.path.join(PKG, "run.py"), "experiment=pixelcnn/synthetic", "datamodule.train_size=128",
+           "datamodule.val_size=32", "datamodule.batch_size=32", "datamodule.width=8", "datamodule.height=8", "model.hidden_dim=16",
+           f"model.class_condition={cond}", "trainer.max_epochs=1", f"log_dir={tmp_path}", "seed=1", "print_config=False"]
+    r = subprocess.run(cmd, cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    run_dir = tmp_path / "runs" / "pixelcnn" / "synthetic"
+    assert (run_dir / "results" / "0.jpg").exists()
+    assert list((run_dir / "checkpoints").glob("*.ckpt"))
+    vals = [json.loads(ln) for ln in (run_dir / "tensorboard" / "metrics.jsonl").read_text().splitlines() if "val_bpd" in ln]
+    assert vals and all(math.isfinite(float(v["val_bpd"])) for v in vals)
