@@ -11,6 +11,7 @@
 // gates.  Matrix cores in both modes: fp32-exact v_mfma_f32_32x32x2_f32 (MI_PCNN_MODE_FP32) or bf16 operands rounded at the MFMA with
 // fp32 accumulation (v_mfma_f32_32x32x16_bf16, MI_PCNN_MODE_BF16); each wave owns a 32 x 32 block, the epilogue reads it back via LDS.
 #include "common.h"
+#include "ar_sample.h"
 
 namespace {
 
@@ -429,28 +430,8 @@ __global__ __launch_bounds__(1024) void pcnn_sample_kernel(int N, int Cc, int H,
                 for (int c = 0; c < Ch; ++c) s = fmaf(elu_f(hr[c]), wr[c], s);
                 l[j] = s;
             }
-            float m = fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3]));
-            for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-            float e[4], run = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { e[j] = expf(l[j] - m); run += e[j]; }
-            float incl = run;                                   // inclusive scan of the lane sums
-            for (int off = 1; off < 64; off <<= 1) {
-                const float v = __shfl_up(incl, off);
-                if (lane >= off) incl += v;
-            }
-            const float total = __shfl(incl, 63);
-            const float inv = 1.f / total, uu = uni[(size_t)pix * N * Cc + u];
-            float cum = incl - run;
-            int pick = 256;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                cum += e[j];
-                if (pick == 256 && cum * inv > uu) pick = lane * 4 + j;
-            }
-            for (int off = 32; off > 0; off >>= 1) pick = min(pick, __shfl_xor(pick, off));
+            const int k = ar_inverse_cdf_pick(l, uni[(size_t)pix * N * Cc + u], lane);
             if (lane == 0) {
-                const int k = pick > 255 ? 255 : pick;
                 float v = (float)k / 255.f;
                 if (normalize) v = v * 2.f - 1.f;
                 img[((size_t)n * Cc + col) * HW + pix] = v;

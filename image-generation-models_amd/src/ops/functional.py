@@ -1885,3 +1885,85 @@ def pcnn_sample_step(h, w, b, counter, uniforms, img, xin, normalize):
 
 def pcnn_zero(t):
     check(load_library().mi_pcnn_zero(_p(t), t.numel() * t.element_size(), _stream()), "mi_pcnn_zero")
+
+
+# ---------------------------------------------------------------------------------------------------------- MADE (csrc/made.hip)
+def made_linear(x, w, b, deg_in, deg_out, act, out=None, mode=MODE_FP32):
+    """y = act(x (W .* M)^T + b), M[o][i] = deg_out[o] >= deg_in[i] (mi_made_linear); act: sigmoid when True.  x [N, in] rows."""
+    _need_gpu(x)
+    N, fin = x.shape
+    fout = w.shape[0]
+    if out is None:
+        out = torch.empty((N, fout), device=x.device)
+    check(load_library().mi_made_linear(mode, N, fin, fout, _p(x), x.stride(0), _p(w), _p(b), _p(deg_in), _p(deg_out), int(act), _p(out),
+                                        out.stride(0), _stream()), "mi_made_linear")
+    return out
+
+
+def made_dgrad(gy, w, deg_in, deg_out, s_in=None, out=None, work=None, mode=MODE_FP32):
+    """dx = (gy (W .* M)) * s_in (1 - s_in) (mi_made_dgrad; s_in None: no factor).  gy [N, out]."""
+    N, fout = gy.shape
+    fin = w.shape[1]
+    lib = load_library()
+    if out is None:
+        out = torch.empty((N, fin), device=gy.device)
+    if work is None:
+        work = torch.empty(lib.mi_made_dgrad_workspace(N, fin, fout) // 4, device=gy.device)
+    check(lib.mi_made_dgrad(mode, N, fin, fout, _p(gy), gy.stride(0), _p(w), _p(deg_in), _p(deg_out), _p(s_in),
+                            0 if s_in is None else s_in.stride(0), _p(work), _p(out), out.stride(0), _stream()), "mi_made_dgrad")
+    return out
+
+
+def made_dgrad_workspace(N, fin, fout):
+    return load_library().mi_made_dgrad_workspace(N, fin, fout) // 4
+
+
+def made_wgrad(gy, x, deg_in, deg_out, dw, db, mode=MODE_FP32):
+    """dW[o][i] = sum_n gy[n][o] x[n][i] on the live entries only, db = column sums of gy (mi_made_wgrad); both written."""
+    N, fout = gy.shape
+    fin = x.shape[1]
+    check(load_library().mi_made_wgrad(mode, N, fin, fout, _p(gy), gy.stride(0), _p(x), x.stride(0), _p(deg_in), _p(deg_out), _p(dw), _p(db),
+                                       _stream()), "mi_made_wgrad")
+
+
+def made_head_fwd(h, w, b, deg_in, deg_out, img, normalize, lse=None, partial=None, loss=None, mode=MODE_FP32):
+    """Fused head -> log-sum-exp -> NLL -> bits per dim (mi_made_head_fwd); img [N, D] (any shape with N rows).  Returns (loss [1], lse [N, D])."""
+    _need_gpu(h)
+    N, Hd = h.shape
+    D = w.shape[0] // 256
+    lib = load_library()
+    if lse is None:
+        lse = torch.empty((N, D), device=h.device)
+    if partial is None:
+        partial = torch.empty(lib.mi_made_head_partials(N, D), device=h.device)
+    if loss is None:
+        loss = torch.empty(1, device=h.device)
+    check(lib.mi_made_head_fwd(mode, N, D, Hd, _p(h), h.stride(0), _p(w), _p(b), _p(deg_in), _p(deg_out), _p(img), int(normalize), _p(lse),
+                               _p(partial), _p(loss), _stream()), "mi_made_head_fwd")
+    return loss, lse
+
+
+def made_head_dlogits(h, w, b, deg_in, deg_out, img, normalize, lse, gscale=None, out=None, mode=MODE_FP32):
+    """dlogits [N, 256 D] = (softmax - onehot) * (*gscale) / (N D ln 2), recomputed from lse (mi_made_head_dlogits)."""
+    N, Hd = h.shape
+    D = w.shape[0] // 256
+    if out is None:
+        out = torch.empty((N, 256 * D), device=h.device)
+    check(load_library().mi_made_head_dlogits(mode, N, D, Hd, _p(h), h.stride(0), _p(w), _p(b), _p(deg_in), _p(deg_out), _p(img),
+                                              int(normalize), _p(lse), _p(gscale), _p(out), _stream()), "mi_made_head_dlogits")
+    return out
+
+
+def made_head_rows(h, w, b, deg_in, deg_out, pos, C, HW, out, mode=MODE_FP32):
+    """logits [N, 256 C] of the C units at raster position *pos (mi_made_head_rows)."""
+    N, Hd = h.shape
+    check(load_library().mi_made_head_rows(mode, N, C, HW, Hd, _p(h), h.stride(0), _p(w), _p(b), _p(deg_in), _p(deg_out), _p(pos), _p(out),
+                                           _stream()), "mi_made_head_rows")
+    return out
+
+
+def made_sample_step(logits, counter, uniforms, img, normalize):
+    """One inverse-CDF step at position *counter (mi_made_sample_step); img [N, C, H, W] written in place."""
+    N, Cc, H, W = img.shape
+    check(load_library().mi_made_sample_step(N, Cc, H * W, _p(logits), _p(counter), _p(uniforms), _p(img), int(normalize), _stream()),
+          "mi_made_sample_step")

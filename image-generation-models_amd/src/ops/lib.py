@@ -227,6 +227,15 @@ SIGNATURES = {
     "mi_pcnn_sample_supported": [_I, _I, _I],
     "mi_pcnn_sample_step": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "mi_pcnn_zero": [_P, _Z, _P],
+    "mi_made_supported": [_I, _I, _I],
+    "mi_made_linear": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P],
+    "mi_made_dgrad": [_I, _I, _I, _I, _P, C.c_longlong, _P, _P, _P, _P, _I, _P, _P, _I, _P],
+    "mi_made_wgrad": [_I, _I, _I, _I, _P, C.c_longlong, _P, _I, _P, _P, _P, _P, _P],
+    "mi_made_head_partials": [_I, _I],
+    "mi_made_head_fwd": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
+    "mi_made_head_dlogits": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
+    "mi_made_head_rows": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "mi_made_sample_step": [_I, _I, _I, _P, _P, _P, _P, _I, _P],
 }
 OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_conv3x3_wgrad_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),
@@ -237,6 +246,7 @@ OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_conv_s2_wgrad_f32_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),
          "mi_f32_to_bf16_colsum_workspace": ([_Z, _I], C.c_size_t),
          "mi_linattn_workspace": ([_I, _I, _I], C.c_size_t),
+         "mi_made_dgrad_workspace": ([_I, _I, _I], C.c_size_t),
          "mi_chan_layernorm_bwd_part_rows": ([_I, _I], C.c_int),
          "mi_conv_small_wgrad_workspace": ([_I], C.c_size_t)}
 ABI_VERSION = 4

@@ -737,6 +737,47 @@ int mi_pcnn_sample_step(int N, int Cc, int H, int W, int Ch, const float* h, int
                         const float* uniforms, float* img, float* xin, int ldx, int normalize, void* stream);
 int mi_pcnn_zero(void* p, size_t bytes, void* stream);
 
+/* ---- MADE operators (reference src/models/made.py; csrc/made.hip) ----------------------------------------------------------------
+ * A masked linear layer y = act(x (W .* M)^T + b) with W the PyTorch [out][in] weight read in place and the mask M given by two
+ * int32 degree vectors: M[o][i] = deg_out[o] >= deg_in[i].  The kernels SELECT the live weights (a masked weight is never read
+ * into a product; a non-finite input meets only live weights), run on fp32-exact MFMA (MI_MADE_MODE_FP32) or on bf16 operands
+ * with fp32 accumulation (MI_MADE_MODE_BF16), and keep every stored value fp32.
+ * mi_made_supported: D = C*H*W >= 1 pixels, C 1..4, hidden a multiple of 4 in 4..8192.
+ * mi_made_linear: y[n][o] = act(sum over live i of x[n][i] W[o][i] + b[o]), act = sigmoid when act != 0.  No atomics: bit-reproducible.
+ * mi_made_dgrad: dx[n][i] = (sum over live o of gy[n][o] W[o][i]) * s(1 - s), s = s_in[n][i] (nullable: no factor); split over o
+ *   into `work` (mi_made_dgrad_workspace bytes), summed in a fixed order.
+ * mi_made_wgrad: dW[o][i] = sum_n gy[n][o] x[n][i] written for the live entries only (masked entries are never written) and
+ *   db[o] = sum_n gy[n][o] (written, not accumulated).
+ * mi_made_head_fwd: the output head (hidden h [N][Hd] -> 256*D logits, unit d*256 + a = class a of pixel d) fused with the
+ *   log-sum-exp and the NLL at the reference's truncated target of img ([N][D] fp32): lse[n][d], partial[mi_made_head_partials],
+ *   *loss = mean bits per dim.  The logits are not written.
+ * mi_made_head_dlogits: dl[n][d*256 + a] = (softmax - onehot) * (*gscale, nullable = 1) / (N*D*ln 2), recomputed from lse.
+ * mi_made_head_rows: logits[n][c*256 + a] of the C units at position *pos of the H*W raster (pixel c*HW + *pos): the sampler's
+ *   head, 256*C rows of the head only.
+ * mi_made_sample_step: at position *counter, for every (sample, channel) k = min{k : cdf_k > u} under the fp32 softmax of its
+ *   logits (clamped to 255; u = uniforms[pos][n*C + c]) written as k/255 (2k/255 - 1 when normalize) into img [N][C][HW] -- unless
+ *   no sample and no channel holds -1 there; then *counter += 1.  One workgroup. */
+#define MI_MADE_MODE_FP32 0
+#define MI_MADE_MODE_BF16 1
+int mi_made_supported(int D, int hidden, int C);
+int mi_made_linear(int mode, int N, int in, int out, const float* x, int ldx, const float* w, const float* b, const int* deg_in,
+                   const int* deg_out, int act, float* y, int ldy, void* stream);
+size_t mi_made_dgrad_workspace(int N, int in, int out);
+int mi_made_dgrad(int mode, int N, int in, int out, const float* gy, long long ldg, const float* w, const int* deg_in, const int* deg_out,
+                  const float* s_in, int lds, float* work, float* dx, int lddx, void* stream);
+int mi_made_wgrad(int mode, int N, int in, int out, const float* gy, long long ldg, const float* x, int ldx, const int* deg_in,
+                  const int* deg_out, float* dw, float* db, void* stream);
+int mi_made_head_partials(int N, int D);
+int mi_made_head_fwd(int mode, int N, int D, int Hd, const float* h, int ldh, const float* w, const float* b, const int* deg_in,
+                     const int* deg_out, const float* img, int normalize, float* lse, float* partial, float* loss, void* stream);
+int mi_made_head_dlogits(int mode, int N, int D, int Hd, const float* h, int ldh, const float* w, const float* b, const int* deg_in,
+                         const int* deg_out, const float* img, int normalize, const float* lse, const float* gscale, float* dl,
+                         void* stream);
+int mi_made_head_rows(int mode, int N, int C, int HW, int Hd, const float* h, int ldh, const float* w, const float* b, const int* deg_in,
+                      const int* deg_out, const int* pos, float* logits, void* stream);
+int mi_made_sample_step(int N, int C, int HW, const float* logits, int* counter, const float* uniforms, float* img, int normalize,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
