@@ -752,6 +752,10 @@ int mi_pcnn_zero(void* p, size_t bytes, void* stream);
  *   log-sum-exp and the NLL at the reference's truncated target of img ([N][D] fp32): lse[n][d], partial[mi_made_head_partials],
  *   *loss = mean bits per dim.  The logits are not written.
  * mi_made_head_dlogits: dl[n][d*256 + a] = (softmax - onehot) * (*gscale, nullable = 1) / (N*D*ln 2), recomputed from lse.
+ *   Non-finite activations: unlike mi_made_linear and mi_made_head_rows, mi_made_head_fwd and mi_made_head_dlogits do NOT take a
+ *   non-finite h out of the matrix-core operand.  A NaN or +-Inf in h[n][i] meets the 0 that stands for a masked weight (NaN * 0 and
+ *   Inf * 0 are NaN), so every logit of row n becomes NaN, whatever the degrees: lse[n][:], the loss and dl[n][:] are NaN.  Training
+ *   feeds them sigmoid outputs, which are finite for every finite input.
  * mi_made_head_rows: logits[n][c*256 + a] of the C units at position *pos of the H*W raster (pixel c*HW + *pos): the sampler's
  *   head, 256*C rows of the head only.
  * mi_made_sample_step: at position *counter, for every (sample, channel) k = min{k : cdf_k > u} under the fp32 softmax of its

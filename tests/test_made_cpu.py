@@ -1,6 +1,7 @@
 """MADE host layer without a GPU: config composition, state_dict contract and seeded init against the reference's fixture,
 the flat buffer, size checks, and the degree vectors recovered from the masks."""
 import hashlib
+import math
 import os
 import sys
 import types
@@ -144,3 +145,119 @@ def test_made_oracle_reproduces_the_fixture(kats):
         for k, g in grads.items():
             r = torch.from_numpy(kats[f"{tag}.grad.{k}"]).double()
             assert float((g - r).abs().max()) <= 1e-4 * max(float(r.abs().max()), 1e-30), k
+
+
+# ---------------------------------------------------------------------------------------------------- kernel-level references
+def _oracle():
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _made_oracle as O
+    return O
+
+
+def _ties_degrees(fin, fout):
+    din = torch.randint(0, 97, (fin,))
+    dout = torch.randint(int(din.min()), int(din.max()) + 1, (fout,))
+    return din.int(), dout.int()
+
+
+@pytest.mark.parametrize("tag,norm", [("u", False), ("c", True)])
+def test_kernel_refs_chain_to_the_model_oracle(kats, tag, norm):
+    """The unrounded layer / head helpers, chained by hand through the tiny fixture net, give bpd_and_grads' bpd and gradients."""
+    from src.models.made import recover_degrees
+    O = _oracle()
+    p = {k[len(tag) + 5:]: torch.from_numpy(kats[k]) for k in kats.files if k.startswith(tag + ".sd0.")}
+    x = torch.from_numpy(kats[tag + ".x"])
+    L = O.n_layers(p)
+    W = [p[f"model.model.{i}.model.weight"] for i in range(L)]
+    B = [p[f"model.model.{i}.model.bias"] for i in range(L)]
+    deg = recover_degrees([p[f"model.model.{i}.mask"] for i in range(L)])
+    acts = [x.reshape(x.shape[0], -1)]
+    for i in range(L - 1):
+        acts.append(O.masked_linear_ref(acts[-1], W[i], B[i], *deg[i], True))
+    for a, r in zip(acts[1:], O.hidden(p, x)):
+        assert float((a - r).abs().max()) <= 1e-13
+    logits, lse, bpd, g = O.head_ref(acts[-1], W[-1], B[-1], *deg[-1], acts[0], norm, chunk=5)
+    ref_logits = O.forward(p, x).permute(0, 2, 3, 4, 1).reshape(logits.shape)
+    assert float((logits - ref_logits).abs().max()) <= 1e-12 * float(ref_logits.abs().max())
+    assert float((lse - torch.logsumexp(ref_logits, -1)).abs().max()) <= 1e-12
+    ref_bpd, grads = O.bpd_and_grads(p, x, norm)
+    assert abs(float(bpd) - float(ref_bpd)) <= 1e-12 * float(ref_bpd)
+
+    def close(a, r, what):
+        assert float((a - r).abs().max()) <= 1e-10 * max(float(r.abs().max()), 1e-300), what
+    for i in range(L - 1, -1, -1):
+        dw, db = O.masked_wgrad_ref(g, acts[i], *deg[i])
+        close(dw, grads[f"model.model.{i}.model.weight"], f"dW{i}")
+        close(db, grads[f"model.model.{i}.model.bias"], f"db{i}")
+        if i:
+            g = O.masked_dgrad_ref(g, W[i], *deg[i], s_in=acts[i])
+
+
+def test_kernel_refs_rounded_operands_rule():
+    """round_bf16 rounds exactly the matrix-core operands, before the mask, and nothing else."""
+    O = _oracle()
+    torch.manual_seed(0)
+    din, dout = _ties_degrees(19, 11)
+    m = O.live_mask(din, dout)
+    x, w, b, gy, s = torch.randn(5, 19), torch.randn(11, 19), torch.randn(11), torch.randn(5, 11), torch.rand(5, 19)
+    rb = lambda t: t.bfloat16().double()
+    assert torch.equal(O.masked_linear_ref(x, w, b, din, dout, True, True), torch.sigmoid(rb(x) @ (rb(w) * m).t() + b.double()))
+    assert torch.equal(O.masked_dgrad_ref(gy, w, din, dout, s, True), (rb(gy) @ (rb(w) * m)) * s.double() * (1 - s.double()))
+    dw, db = O.masked_wgrad_ref(gy, x, din, dout, True)
+    assert torch.equal(dw, (rb(gy).t() @ rb(x)) * m) and torch.equal(db, gy.double().sum(0))
+    assert not torch.equal(O.masked_linear_ref(x, w, b, din, dout, True, True), O.masked_linear_ref(x, w, b, din, dout, True, False))
+    D = 3
+    hdin = torch.randint(0, D, (19,)).int()
+    hdout = (torch.arange(D).repeat_interleave(256) - 1).int()
+    hw, hb, img = torch.randn(256 * D, 19), torch.randn(256 * D), torch.randint(0, 256, (5, D)).float() / 255
+    lg, lse, bpd, dl = O.head_ref(x, hw, hb, hdin, hdout, img, False, True, gscale=2.0)
+    want = (rb(x) @ (rb(hw) * O.live_mask(hdin, hdout)).t() + hb.double()).reshape(5, D, 256)
+    assert torch.equal(lg, want) and torch.equal(lg[:, 0], hb[:256].double().expand(5, 256))
+    assert float(dl.reshape(5, D, 256).sum(-1).abs().max()) <= 1e-15
+    t = O.target(img, False)
+    nll = torch.nn.functional.cross_entropy(want.reshape(-1, 256), t.reshape(-1), reduction="sum")
+    assert abs(float(bpd) - float(nll) / (5 * D * math.log(2.0))) <= 1e-13 * float(bpd)
+
+
+@pytest.mark.parametrize("n,fin,fout", [(128, 784, 1024), (128, 1024, 1024), (3, 27, 40), (16, 4096, 8)])
+def test_rounded_operands_leave_only_fp32_accumulation(n, fin, fout):
+    """bf16 x bf16 products are exact in fp32.  With both operands rounded as the kernel rounds them, an fp32 evaluation of the
+    forward, the data gradient and the weight gradient lies within 1e-6 of max |fp64 value| (measured: <= 4e-7 on these shapes,
+    the last one a 4096-long signed contraction).  This is the evidence that 1e-5 is a fair bound for the GPU's bf16 mode."""
+    O = _oracle()
+    torch.manual_seed(n + fin)
+    din, dout = _ties_degrees(fin, fout)
+    m = O.live_mask(din, dout)
+    w, b = torch.randn(fout, fin) / math.sqrt(fin), torch.randn(fout) * 0.1
+    x = torch.rand(n, fin) if fin != 4096 else torch.randn(n, fin)
+    gy = torch.randn(n, fout)
+    r32 = lambda t: t.bfloat16().float()
+
+    def rel(a, ref):
+        return float((a.double() - ref).abs().max()) / float(ref.abs().max())
+    errs = (rel(r32(x) @ (r32(w) * m).t() + b, O.masked_linear_ref(x, w, b, din, dout, False, True)),
+            rel(r32(gy) @ (r32(w) * m), O.masked_dgrad_ref(gy, w, din, dout, None, True)),
+            rel((r32(gy).t() @ r32(x)) * m, O.masked_wgrad_ref(gy, x, din, dout, True)[0]))
+    print("fp32 evaluation of the rounded operands vs fp64:", errs)
+    assert max(errs) <= 1e-6, errs
+
+
+def test_dlogits_zero_sum_fp32_floor():
+    """What an fp32 evaluation of exp(v - lse) - onehot leaves of the zero sum over a pixel's 256 classes (in units of the dlogits'
+    scale factor), summed in fp32 and in fp64.  Measured: 6.3e-7 (= _made_oracle.ZERO_SUM_FP32; lse is 4..8, so half an ulp of it
+    alone moves the sum by 2.4e-7).  tests/test_made_kernels_gpu.py allows the GPU 4x that for its own expf and summation order."""
+    O = _oracle()
+    torch.manual_seed(7)
+    worst = 0.0
+    for n, hd, D in ((96, 36, 48), (200, 64, 35), (64, 1024, 16)):
+        din = torch.randint(0, D, (hd,)).int()
+        dout = (torch.arange(D).repeat_interleave(256) - 1).int()
+        w, b, h = torch.randn(256 * D, hd) / math.sqrt(hd), torch.randn(256 * D) * 0.1, torch.rand(n, hd)
+        t = torch.randint(0, 256, (n, D))
+        v = (h @ (w * O.live_mask(din, dout)).t() + b).reshape(n, D, 256)
+        lse = torch.logsumexp(v, -1)
+        dl = torch.exp(v - lse[..., None])
+        dl.scatter_add_(-1, t[..., None], torch.full((n, D, 1), -1.0))
+        worst = max(worst, float(dl.sum(-1).abs().max()), float(dl.double().sum(-1).abs().max()))
+    print("zero-sum floor of the fp32 evaluation:", worst)
+    assert worst <= 1.05 * O.ZERO_SUM_FP32

@@ -50,7 +50,9 @@ CONVS = [("v", 3, 1, False), ("v", 3, 2, False), ("v", 3, 4, False), ("h", 3, 1,
 @pytest.mark.parametrize("cin,hw,n", [(1, (28, 28), 2), (3, (32, 32), 2), (8, (7, 5), 3), (64, (64, 64), 1)])
 def test_masked_conv_fwd_dgrad_wgrad(kind, k, dil, mc, cin, hw, n, mode):
     """fp32 mode: fp32-exact MFMA, <= 1e-5 of max |ref|.  bf16 mode: operands rounded to bf16 (2^-9 relative each) and fp32
-    accumulation: <= 2e-2 of max |ref| against the fp32 reference."""
+    accumulation: <= 2e-2 of max |ref| against the fp32 reference, and <= 1e-5 against the float64 convolution of the operands
+    rounded the same way (x and w * mask for the forward, dy and the other operand for the gradients; the bias unrounded): bf16 x
+    bf16 products are exact in fp32, so only fp32 accumulation order is left."""
     from src.models.pixelcnn import horizontal_mask, live_taps, vertical_mask
     K = _K()
     H, W = hw
@@ -77,6 +79,14 @@ def test_masked_conv_fwd_dgrad_wgrad(kind, k, dil, mc, cin, hw, n, mode):
     K.pcnn_wgrad(_nhwc(x.detach()), _nhwc(dy), dw, taps, (T, cin * T), mode=md)
     assert _rel(dw.cpu() * mask, wm.grad * mask) <= tol
     assert float((dw.cpu() * (1 - mask)).abs().max()) == 0.0           # masked taps: never written
+    if mode == "bf16":
+        rb = lambda t: t.detach().bfloat16().double()
+        xr, wr = rb(x).requires_grad_(), rb(w * mask).requires_grad_()
+        ref_r = F.conv2d(xr, wr, b.double(), padding=pad, dilation=dil)
+        ref_r.backward(rb(dy))
+        errs = (_rel(_nchw(y), ref_r), _rel(_nchw(dx), xr.grad), _rel(dw.cpu() * mask, wr.grad * mask))
+        print("bf16 mode against the operand-rounded float64 reference (y, dx, dw):", errs)
+        assert max(errs) <= 1e-5, errs
 
 
 # ------------------------------------------------------------------ 2. gated epilogue (with the 1x1 second source) and gate backward
