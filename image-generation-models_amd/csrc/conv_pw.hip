@@ -20,8 +20,8 @@
 //   * 66 KB of LDS and <= 256 registers per lane: two workgroups per CU -- one computes while the other waits for its first rows or
 //     drains its stores.
 // What it measures (B = 128, bf16 in / out, tools/bench_pw.py; round 2's per-shape pick beside it): 128 -> 128 @32x32 38-39 us (52-54),
-// 256 -> 256 @16x16 34 us (41-43), 512 -> 512 @8x8 33.5-34.7 us (43-45) = 1.11-1.15 PFLOP/s.  Ablations of this structure (profiling
-// build, tools/abl_pw.sh): the DPP shifts are free (<= 4 %), waiting for loads is free (a build that never waits: +-1 %), what
+// 256 -> 256 @16x16 34 us (41-43), 512 -> 512 @8x8 33.5-34.7 us (43-45) = 1.11-1.15 PFLOP/s.  Ablations of this structure (round 3's
+// profiling builds, docs/history/): the DPP shifts are free (<= 4 %), waiting for loads is free (a build that never waits: +-1 %), what
 // costs is ISSUING vector-memory instructions next to the MFMA stream -- without the fragment loads -19 % on the deep layers,
 // without the activation DMA -16 %, without the output stores -7..12 %; the same time with one and with two waves per SIMD.
 // Round 5 ("Round 5"; tools/pw_timeline.py with -DMI_PW_TIMING): the plain bf16 / fp32-input conv (VAR 0 / 1) runs a PINNED,
@@ -36,35 +36,11 @@
 #ifndef MI_PW_PABL
 #define MI_PW_PABL 0     // profiling builds: 1 no fragment requests in the pinned loop, 2 no piece requests, 4 no step-opening wait, 8 no shifts, 16 no barrier
 #endif
-#ifndef MI_PW_SPIECE
-#define MI_PW_SPIECE 1    // scalar piece addressing in the plain conv (0: stage_x's per-lane 64-bit addresses)
-#endif
-#ifndef MI_PW_SKEW
-#define MI_PW_SKEW 0      // 16-cycle units of delay per wave index behind every barrier of the pinned loop
-#endif
-#ifndef MI_PW_RSTAGE
-#define MI_PW_RSTAGE 1    // pinned loop: the next chunk's pieces through registers (global_load + ds_write_b128) instead of LDS-DMA
-#endif
-#ifndef MI_PW_ROT
-#define MI_PW_ROT 1       // per-workgroup rotation of the chunk order
-#endif
-#ifndef MI_PW_WSTR
-#define MI_PW_WSTR 2
-#endif
-#ifndef MI_PW_PIPE
-#define MI_PW_PIPE 1      // 0: round 3 / 4's compiler-scheduled main loop for the plain conv too (A/B builds)
-#endif
 #ifndef MI_PW_GNSABL
 #define MI_PW_GNSABL 0    // profiling builds of the GroupNorm-sums epilogue: 1 no reduction / atomics, 2 no per-element sums (bf16 tile path)
 #endif
-#ifndef MI_PW_GNSW
-#define MI_PW_GNSW 0
-#endif
 #ifndef MI_PW_FXABL
 #define MI_PW_FXABL 0     // profiling builds of the pinned fused loop: 1 no transform, 2 unpacked fp32 instructions
-#endif
-#ifndef MI_PW_FPIPE
-#define MI_PW_FPIPE 3     // round 6: the fused GroupNorm + Mish variants (VAR 2 / 3) on the pinned loop -- bit 0 bf16 input, bit 1 fp32 input (0: round 4's loop, A/B builds)
 #endif
 #ifdef MI_PW_TIMING
 // profiling build only (-DMI_PW_TIMING, tools/pw_timeline.py): shader-clock stamps (s_memtime) at every row unit of conv_pw_kernel's main
@@ -180,33 +156,29 @@ template <int DIR, int HALF> __device__ __forceinline__ void pw_shift_h(u32x4& o
     o[2 * HALF] = a0; o[2 * HALF + 1] = a1;
 }
 
-constexpr int pw_lds(int pt, bool raw = false) { return (pt == 256 ? 128 : pt == 128 ? (raw ? 72 : 64) : (raw ? 48 : 32)) * 1024 + 2048; }   // two activation buffers (24 / 16 KB each) under the epilogue's fp32 tile (+ the GroupNorm sums' 512 bytes); raw: + the fp32 staging area of the fp32-input variants (24 / 16 KB behind the tiles)
+constexpr int pw_lds(int pt, bool raw = false) { return (pt == 256 ? 128 : pt == 128 ? (raw ? 72 : 64) : (raw ? 48 : 32)) * 1024 + 2048; }   // two activation buffers (24 / 16 KB each) under the epilogue's fp32 tile (+ the GroupNorm sums' 512 bytes); raw (plain fp32 input): + 8 / 16 KB that an earlier LDS staging of the fp32 pieces used -- nothing writes them now; the launch is kept as it was measured
 
 // VAR 0: the plain conv.  VAR 1: the epilogue also accumulates the GroupNorm sums of the NEXT layer (a.gsum).  VAR 2 / 3: the named
 // fused kernel (2: coefficients given, 3: resolved here from the producer's sums) -- x is the RAW output of the previous conv and mish(x * scale[n][c] + shift[n][c]) + tb[n][c] (a.coef; GroupNorm-apply
 // + Mish + time bias, reference src/models/ddpm.py:112-120,139-141) is applied ONCE per staged element: every wave transforms the
-// pieces it requested itself as one block per chunk (bf16 input: in place in LDS; fp32 input: from the raw staging area, half a chunk
-// at a time) before the chunk barrier publishes them; rows outside the image stay zero.  One image per tile (TI == 1).
-// ABL (profiling builds only, -DMI_PW_ABL_BUILD): 1 no fragment DMA in the main loop, 2 no activation DMA in the main loop, 4 no stores,
-// 16 no DPP shifts (every tap column multiplies the centre fragments), 32 loads issued but never waited for in the main loop
-// IN32: x / x2 are fp32 tensors (the residual stream: the sampler's block1 convs, fp32 block storage).  Their raw pieces arrive by
-// LDS-DMA in a staging area behind the two bf16 tiles, half a chunk at a time; each lane reads back its own 8 channels, rounds them to
-// bf16 once and writes the 16 bytes of its slot of the tile -- the lane requests the channel chunk that belongs in ITS slot, as the
-// DMA's source addresses do for bf16 input.  (Round 3 staged two pieces per step through registers with counted waits; only the
-// prologue still does.)
-// IN32 + VAR 2 / 3 (round 4; the named fused kernel for fp32-stored activations): the transform is applied to the fp32 values while
-// they sit in those registers, between their load and the one rounding -- no LDS read-modify-write, no unpack.
+// pieces it requested itself in the registers they were loaded into, before the chunk barrier publishes them; rows outside the image
+// stay zero.  One image per tile (TI == 1).
+// IN32: x / x2 are fp32 tensors (the residual stream: the sampler's block1 convs, fp32 block storage).  A piece is two 16-byte loads
+// per lane (its own 8 channels -- the lane requests the channel chunk that belongs in ITS slot of the tile), rounded to bf16 once
+// and written to that slot; with VAR 2 / 3 the transform is applied to the fp32 values between their load and the one rounding.
+// The third template parameter is always 0: it is kept for the kernel symbols that profiles and tests have recorded.
 // F32: the exact-fp32 mode of the same kernel (Unet.compute_mode = "fp32", the reference's default precision and the mode that carries
 // the 1e-4 parity bar): x / x2 / y fp32, weights fp32 in fragment order [tap][co / 32][ci / 8][lane][4] (mi_pack_weights_f32frag),
 // v_mfma_f32_32x32x2_f32 -- bit-equal to an fp32 fmaf chain.  Everything keeps its byte geometry: a 16-byte piece of a pixel row is 4
 // fp32 channels instead of 8 bf16 ones, so a chunk is 32 channels, a step 8, a fragment is still 1 KB and feeds four MFMAs per block
 // (k = 2 each: lane half h supplies channel 4h + j of the octet in step j).  Per 16 bytes loaded the fp32 MFMA runs 8x longer than
 // the bf16 one, so this variant is bound by the matrix pipe, not by the issue of loads.
-template <bool OUT16, int VAR = 0, int ABL = 0, int PT = 128, bool IN32 = false, bool F32 = false>
+template <bool OUT16, int VAR = 0, int ZERO = 0, int PT = 128, bool IN32 = false, bool F32 = false>
 __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const PwArgs a) {
     MI_PRIO_UP();
+    static_assert(ZERO == 0, "unused: kept so that the recorded kernel symbols (profiles, launch-name tests) stay valid");
 #ifdef MI_PW_TIMING
-    constexpr bool TIMED = VAR == 0 && ABL == 0 && !IN32 && !F32;
+    constexpr bool TIMED = VAR == 0 && !IN32 && !F32;
     uint32_t tv[5] = {0u, 0u, 0u, 0u, 0u};
     uint64_t tprev = 0;
     if constexpr (TIMED) {
@@ -222,13 +194,11 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
 #endif
     static_assert(PT != 256 || (VAR < 2 && !IN32 && !F32), "256-pixel tiles: the plain bf16 conv (with or without the GroupNorm sums)");
     constexpr bool FUSE = VAR >= 2, GNS = VAR == 1;
-    // round 6: the fused variants on round 5's pinned loop.  The coefficients of ALL K channels of the tile's image (scale log2(e), shift log2(e),
+    // round 6: the fused variants run round 5's pinned loop.  The coefficients of ALL K channels of the tile's image (scale log2(e), shift log2(e),
     // time bias: 12 bytes per channel, built once in the prologue) wait in LDS behind the two activation buffers, a piece of the next chunk is
     // transformed in the registers it was loaded into (no LDS read-modify-write) and its work -- coefficient reads, two Mish pairs per half piece,
     // the ds_write_b128 -- rides in the MFMA gaps of steps 2 and 3 like the plain conv's register staging; the counted waits are the plain conv's.
-    constexpr bool FPIPE = FUSE && !F32 && ABL == 0 && (MI_PW_PIPE != 0) && (((MI_PW_FPIPE) >> (IN32 ? 1 : 0)) & 1) != 0;
-    static_assert(!IN32 || ABL == 0, "fp32 input: no ablation builds");
-    static_assert(!F32 || (VAR == 0 && ABL == 0 && !IN32 && !OUT16), "exact-fp32 mode: the plain conv, fp32 in and out");
+    static_assert(!F32 || (VAR == 0 && !IN32 && !OUT16), "exact-fp32 mode: the plain conv, fp32 in and out");
     constexpr int PCK = F32 ? 32 : 64;                       // channels per chunk (128 bytes of a pixel row)
     constexpr int ESZ = F32 ? 4 : 2, EPP = 16 / ESZ;         // element size, elements per 16-byte piece
     constexpr int BH = PT / 32;                              // rows per band = 32-pixel blocks per wave
@@ -260,7 +230,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
     // nchunks).  The workgroups of a channel tile otherwise request the SAME weight lines in the same microseconds -- 16 CUs of an XCD on a
     // handful of L2 channels -- and the per-chunk time stayed at ~6 000 cycles whatever was done about issue order, waits or staging.
     // (The sum of a pixel's products is formed in a different order per tile: deterministic, tile by tile.)
-    const int rot = MI_PW_ROT ? bx - pw_fastdiv(bx, a.nch_magic) * nchunks : 0;
+    const int rot = bx - pw_fastdiv(bx, a.nch_magic) * nchunks;
     auto cof = [&](int ch) -> int { const int c = min(ch, nchunks - 1) + rot; return kbase + (c >= nchunks ? c - nchunks : c); };
 
     // ---- weight stream of this wave: fragment (tap, nb, kq) = 1 KB at ((tap * NB + nb) * KQ + kq) * 1024 bytes.  The fragments are
@@ -337,7 +307,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         }
     }
     const uint16_t* zero = reinterpret_cast<const uint16_t*>(a.zero);
-    auto stage_x = [&](int ch, int i) {                      // piece i of this wave of chunk ch's rows -> buffer ch & 1
+    auto stage_x = [&](int ch, int i) {                      // exact-fp32 mode: piece i of this wave of chunk ch's rows -> buffer ch & 1 (LDS-DMA)
         const int cc0 = cof(ch) * PCK;
         const bool second = cc0 >= a.K1;
         const uint16_t* src = second ? a.x2 : a.x;
@@ -350,18 +320,17 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         const uint8_t* p = xp >= 0 ? reinterpret_cast<const uint8_t*>(src) + off * ESZ : reinterpret_cast<const uint8_t*>(zero) + (l & 7) * 16;
         glds16(p, lds0 + (ch & 1) * PXBUF + (wv + 4 * i) * 1024);
     };
-    // ---- round 5, the plain conv: a piece = 8 pixels of ONE tile row (W >= 8), so everything about it but the lane's place in it is
+    // ---- round 5, the bf16 MFMA mode: a piece = 8 pixels of ONE tile row (W >= 8), so everything about it but the lane's place in it is
     //      wave-uniform: source = scalar base (tensor + row + chunk) + a per-lane offset that is the same for every piece and chunk
     //      ((l >> 3) pixels + the lane's channel slot), i.e. no vector arithmetic per request at all (stage_x: a 64-bit multiply-add, a
     //      compare and two selects per piece).  A piece outside the image is not fetched from a zero page: its LDS rows are zeroed once
     //      (both buffers) and its request -- still issued, the counted waits assume it -- reads valid memory into a dump area.
-    constexpr bool SPIECE = (((MI_PW_SPIECE != 0 || IN32) && VAR < 2) || FPIPE) && !F32 && ABL == 0;     // (fp32 input, fused: the pinned loop's register staging needs it)
     constexpr int XSZ = IN32 ? 4 : ESZ;                     // bytes per element of x / x2 in memory
-    int prow[SPIECE ? PXPW : 1];                             // first pixel of the piece in the tensor, 0 when outside (scalar)
+    int prow[F32 ? 1 : PXPW];                                // first pixel of the piece in the tensor, 0 when outside (scalar)
     uint32_t pvalid = 0;                                     // bit i: piece i lies in the image
     uint32_t lane_off1 = 0, lane_off2 = 0;
     constexpr uint32_t DUMP = 2 * PXBUF;                     // 1 KB behind the two tiles (the epilogue's tile starts over)
-    if constexpr (SPIECE) {
+    if constexpr (!F32) {
         const int y0s = a.TI > 1 ? 0 : (bx - img0 * a.tiles_per_img) * a.TH;
 #pragma unroll
         for (int i = 0; i < PXPW; ++i) {
@@ -386,7 +355,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         glds16s(sb, second ? lane_off2 : lane_off1, dst);
     };
     if constexpr (EARLYW) {                                  // the first chunk's rows: on their way before the rest of the set-up
-        if constexpr (SPIECE) {
+        if constexpr (!F32) {
             static_for<0, PXPW>([&](auto ic) { stage_s(0, ic); });
             typedef __attribute__((address_space(3))) u32x4 lds_u32x4z;
 #pragma unroll
@@ -401,7 +370,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    // fp32 input: piece i of chunk ch -> the two registers of `dst` (8 channels of this lane's pixel), asynchronous
+    // plain fp32 input, prologue: piece i of chunk ch -> the two registers of `dst` (8 channels of this lane's pixel), asynchronous
     auto load_x32 = [&](int ch, int i, u32x4* dst) {
         const int cc0 = cof(ch) * PCK;
         const bool second = cc0 >= a.K1;
@@ -519,68 +488,23 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         constexpr int e = decltype(ec)::value;
         return f32x2{cq[2 * k + (e >> 2)][e & 3], cq[2 * k + (e >> 2)][(e & 3) + 1]};
     };
-    auto tpart = [&](uint32_t v, auto qc, uint32_t vmask) -> uint32_t {
+    // (chunk 0's pieces, transformed in the prologue before the coefficient table is published; pieces outside the image go to the dump area)
+    auto tpart = [&](uint32_t v, auto qc) -> uint32_t {
         constexpr int q = decltype(qc)::value;
         constexpr std::integral_constant<int, 2 * q> E{};
         const f32x2 x = {__uint_as_float(v << 16), __uint_as_float(v & 0xffff0000u)};
         const f32x2 m = mish_tb2(x, cq2(0, E), cq2(1, E), cq2(2, E));
-        return pack_bf16(m.x, m.y) & vmask;                  // rows above / below the image stay zero padding
-    };
-    auto piece_addr = [&](int buf, int i) -> uint32_t { return lds0 + buf * PXBUF + (wv + 4 * i) * 1024 + l * 16; };
-    auto piece_mask = [&](int i) -> uint32_t {
-        uint32_t m = xpix[i] >= 0 ? ~0u : 0u;
-        asm volatile("" : "+v"(m));                          // a mask, not a branch around the arithmetic
-        return m;
+        return pack_bf16(m.x, m.y);
     };
     typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
     // fp32 input: half h (elements 4h .. 4h + 3 of the lane's 8 channels) of a piece in registers -> two packed registers of `dst`
-    auto xhalf = [&](const u32x4& r, auto hc, uint32_t vmask, u32x4& dst) {
+    auto xhalf = [&](const u32x4& r, auto hc, u32x4& dst) {
         constexpr int h = decltype(hc)::value;
         constexpr std::integral_constant<int, 4 * h> E0{};
         constexpr std::integral_constant<int, 4 * h + 2> E1{};
         const f32x2 m0_ = mish_tb2(f32x2{__uint_as_float(r.x), __uint_as_float(r.y)}, cq2(0, E0), cq2(1, E0), cq2(2, E0));
         const f32x2 m1_ = mish_tb2(f32x2{__uint_as_float(r.z), __uint_as_float(r.w)}, cq2(0, E1), cq2(1, E1), cq2(2, E1));
-        dst[2 * h] = pack_bf16(m0_.x, m0_.y) & vmask; dst[2 * h + 1] = pack_bf16(m1_.x, m1_.y) & vmask;
-    };
-
-    // fp32 input, fused (round 4): raw staging area behind the two bf16 buffers -- [wave][slot 0..2][2 KB]: a piece = 8 pixels x 64 fp32
-    // channels = two DMA instructions; lane l fetches channels xcol + 4 j .. + 3 (j = 0, 1) of ITS pixel, so that the same lane reads
-    // back its own 8 channels (conflict-free by construction), transforms them and writes the 16 bf16 bytes of its slot of the tile
-    constexpr uint32_t RAW0 = 2 * PXBUF;
-    constexpr int RHP = PXPW / 2;                            // pieces per half chunk and wave (= staging slots): 3 (128-pixel tiles) or 2
-    auto stage_raw = [&](int ch, int i, int slot) {
-        const int cc0 = cof(ch) * PCK;
-        const bool second = cc0 >= a.K1;
-        const float* src = reinterpret_cast<const float*>(second ? a.x2 : a.x);
-        const int ld = second ? a.ldx2 : a.ldx, cc = second ? cc0 - a.K1 : cc0;
-        int xp = xpix[i];
-        asm volatile("" : "+v"(xp));
-        size_t off = (size_t)max(xp, 0) * ld + cc + xcol;
-        asm volatile("" : "+v"(off));
-        const float* pf = xp >= 0 ? src + off : reinterpret_cast<const float*>(a.zero) + (l & 7) * 8;
-        glds16(pf, lds0 + RAW0 + (wv * RHP + slot) * 2048);
-        glds16(pf + 4, lds0 + RAW0 + (wv * RHP + slot) * 2048 + 1024);
-    };
-    auto raw_half = [&](int buf, int half) {                  // pieces RHP half .. of this wave: staging area -> transformed bf16 tile
-        typedef __attribute__((address_space(3))) u32x4 lds_u32x4r;
-        u32x4 rv[RHP][2];
-#pragma unroll
-        for (int i = 0; i < RHP; ++i) {
-            rv[i][0] = *(lds_u32x4r*)(uintptr_t)(lds0 + RAW0 + (wv * RHP + i) * 2048 + l * 16);
-            rv[i][1] = *(lds_u32x4r*)(uintptr_t)(lds0 + RAW0 + (wv * RHP + i) * 2048 + 1024 + l * 16);
-        }
-#pragma unroll
-        for (int i = 0; i < RHP; ++i) {
-            u32x4 o;
-            if constexpr (FUSE) {
-                const uint32_t vm = piece_mask(RHP * half + i);
-                xhalf(rv[i][0], std::integral_constant<int, 0>{}, vm, o); xhalf(rv[i][1], std::integral_constant<int, 1>{}, vm, o);
-            } else {                                         // the plain conv: one rounding (rows outside the image were read from the zero page)
-                o = u32x4{pack_bf16(__uint_as_float(rv[i][0].x), __uint_as_float(rv[i][0].y)), pack_bf16(__uint_as_float(rv[i][0].z), __uint_as_float(rv[i][0].w)),
-                          pack_bf16(__uint_as_float(rv[i][1].x), __uint_as_float(rv[i][1].y)), pack_bf16(__uint_as_float(rv[i][1].z), __uint_as_float(rv[i][1].w))};
-            }
-            *(lds_u32x4r*)(uintptr_t)piece_addr(buf, RHP * half + i) = o;
-        }
+        dst[2 * h] = pack_bf16(m0_.x, m0_.y); dst[2 * h + 1] = pack_bf16(m1_.x, m1_.y);
     };
 
     // ---- fragment addressing.  A 32-pixel MFMA block = output row i (0..3) of every 4-row band of the tile: lane q = l & 31 ->
@@ -610,33 +534,21 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
     for (int i = 0; i < BH; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-    bf16x8 XA, XB, XP, XQ;                                   // centre fragments: rows 0 and BH + 1 of a step; odd / even rows 1 .. BH
 
-    // bf16 output: the bias of this lane's four channel quads, requested before anything else and used only by the epilogue (there a
-    // load would put an HBM round trip in front of the tile's way out)
-    // (round 5, pinned loop: the 128 bias values of the tile wait in LDS instead of 16 registers per lane)
-    constexpr bool PIPE_ = (MI_PW_PIPE != 0) && (VAR < 2 || FPIPE) && !F32 && ABL == 0;
+    // bf16 output: the 128 bias values of the tile, requested before anything else and used only by the epilogue (there a load would
+    // put an HBM round trip in front of the tile's way out); they wait in LDS, not in 16 registers per lane
     constexpr uint32_t BIASL = 2 * PXBUF + 1024;             // 512 bytes behind the dump area
-    constexpr uint32_t COEFL = 2 * PXBUF + 2048;             // FPIPE: the coefficient table, [K / 4][scale x 4, shift x 4, time bias x 4] = 12 K bytes
-    f32x4 bias_q[(OUT16 && !FUSE) ? 4 : 1];
-    if constexpr (OUT16 && (!FUSE || FPIPE) && PIPE_) {
+    constexpr uint32_t COEFL = 2 * PXBUF + 2048;             // fused: the coefficient table, [K / 4][scale x 4, shift x 4, time bias x 4] = 12 K bytes
+    if constexpr (OUT16) {
         typedef __attribute__((address_space(3))) f32x4 lds_f32x4b;
         if (t < 32) {
             f32x4 bv = {0.f, 0.f, 0.f, 0.f};
             if (a.bias && n0 + 4 * t < a.Nc) bv = *reinterpret_cast<const f32x4*>(a.bias + n0 + 4 * t);
             *(lds_f32x4b*)(uintptr_t)(lds0 + BIASL + 16 * t) = bv;
         }
-    } else
-    if constexpr (OUT16 && !FUSE) {
-#pragma unroll
-        for (int rq = 0; rq < 4; ++rq) {
-            bias_q[rq] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (a.bias && live) bias_q[rq] = *reinterpret_cast<const f32x4*>(a.bias + n0 + 4 * (8 * wv + 2 * rq + (l >> 5)));
-        }
     }
-    // ---- prologue: the first chunk's rows, the first step's fragments
-    if constexpr (!EARLYW) MI_PW_NOW(10);
-    // ---- fused variants on the pinned loop: table operands (oldest requests), the first step's fragments, chunk 0's pieces through registers
+    // ---- prologue (the plain bf16 / exact-fp32 conv's requests left above): the first chunk's rows, the first step's fragments
+    // ---- fused variants: table operands (oldest requests), the first step's fragments, chunk 0's pieces through registers
     constexpr int RSNF = IN32 ? 2 : 1;
     auto fx_read = [&](int ch, auto hc, f32x4 (&cf)[3]) {      // coefficients of half h (4 channels) of this lane's slot of chunk ch
         constexpr int h = decltype(hc)::value;
@@ -675,7 +587,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         o[2 * h] = pack_bf16(m0_.x, m0_.y); o[2 * h + 1] = pack_bf16(m1_.x, m1_.y);
 #endif
     };
-    if constexpr (FPIPE) {
+    if constexpr (FUSE) {
         // issue order = landing order: the statistics (VAR 3), this lane's coefficients of chunk 0 (registers: chunk 0 is transformed before
         // the table is published), the table's operands, the first step's fragments, chunk 0's pieces
         if constexpr (VAR == 3) load_stats();
@@ -739,84 +651,26 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
             u32x4 o;
             if constexpr (IN32) {
                 landed16(pr[i][1]);
-                xhalf(pr[i][0], std::integral_constant<int, 0>{}, ~0u, o); xhalf(pr[i][1], std::integral_constant<int, 1>{}, ~0u, o);
+                xhalf(pr[i][0], std::integral_constant<int, 0>{}, o); xhalf(pr[i][1], std::integral_constant<int, 1>{}, o);
             } else {
-                static_for<0, 4>([&](auto qc) { o[decltype(qc)::value] = tpart(pr[i][0][decltype(qc)::value], qc, ~0u); });
+                static_for<0, 4>([&](auto qc) { o[decltype(qc)::value] = tpart(pr[i][0][decltype(qc)::value], qc); });
             }
             const uint32_t off = ((pvalid >> i) & 1u) ? (uint32_t)(4 * i * 1024) : (uint32_t)(DUMP - wv * 1024);
             *(lds_u32x4*)(uintptr_t)(lds0 + wv * 1024 + l * 16 + off) = o;
         });
-    }
-    if constexpr (VAR == 3 && !FPIPE) load_stats();
-    if constexpr (FUSE && !FPIPE) load_coef(0);
-    if constexpr (FPIPE) {
-    } else if constexpr (IN32) {
+    } else if constexpr (IN32) {                             // plain fp32 input: chunk 0's pieces through registers, one rounding
         u32x4 pr[PXPW][2];
 #pragma unroll
         for (int i = 0; i < PXPW; ++i) load_x32(0, i, pr[i]);
         static_for<0, NPART>([&](auto pc) { load_w3(0, std::integral_constant<int, 0>{}, pc); });
-        if constexpr (VAR == 3) {                            // the statistics are the oldest requests: their arithmetic runs under the rows' flight
-            asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + 2 * PXPW + 9) : "memory");
-            stats_landed();
-        }
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");     // the rows of chunk 0 (and, older, the coefficients)
-        if constexpr (FUSE) {
-            coef_landed(0);
+        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");     // the rows of chunk 0
 #pragma unroll
-            for (int i = 0; i < PXPW; ++i) {
-                landed16(pr[i][0]); landed16(pr[i][1]);
-                const uint32_t vm = piece_mask(i);
-                u32x4 o;
-                xhalf(pr[i][0], std::integral_constant<int, 0>{}, vm, o); xhalf(pr[i][1], std::integral_constant<int, 1>{}, vm, o);
-                *(lds_u32x4*)(uintptr_t)piece_addr(0, i) = o;
-            }
-        } else {
+        for (int i = 0; i < PXPW; ++i) store_x32(0, i, pr[i]);
+        // pieces outside the image are never written again (buffer 0 just got its zeros)
+        typedef __attribute__((address_space(3))) u32x4 lds_u32x4z;
 #pragma unroll
-            for (int i = 0; i < PXPW; ++i) store_x32(0, i, pr[i]);
-            if constexpr (SPIECE) {                          // pinned loop: pieces outside the image are never written again (buffer 0 just got its zeros)
-                typedef __attribute__((address_space(3))) u32x4 lds_u32x4z;
-#pragma unroll
-                for (int i = 0; i < PXPW; ++i)
-                    if (!((pvalid >> i) & 1u)) *(lds_u32x4z*)(uintptr_t)(lds0 + PXBUF + (wv + 4 * i) * 1024 + l * 16) = u32x4{0u, 0u, 0u, 0u};
-            }
-        }
-    } else {
-        if constexpr (!EARLYW) {
-#pragma unroll
-            for (int i = 0; i < PXPW; ++i) stage_x(0, i);
-            static_for<0, NPART>([&](auto pc) { load_w3(0, std::integral_constant<int, 0>{}, pc); });
-        }
-    }
-    // bf16 input, fused: this wave's six pieces of a chunk, rewritten in place in LDS in ONE go -- three pieces (twelve independent
-    // exp -> rcp chains per lane) in flight at a time.  Round 4: the main loop does this at the chunk boundary instead of spreading
-    // the parts over the units of the steps (two element pairs per unit, "under" the MFMAs): a wave issues in order, so the two
-    // dependent transcendental chains of a unit stalled the MFMAs queued behind them -- the interleaved form cost 4.3 us per chunk of
-    // a level-0 launch, the same work as a block 1.5 us (the other workgroup of the CU owns the matrix pipe meanwhile), and the block
-    // can be skipped for the last chunk, which has no successor (a third of the transforms at K = 128).
-    constexpr int HP = PXPW / 2;                             // pieces per half chunk and wave: 3 (128-pixel tiles) or 2
-    auto transform_chunk = [&](int buf) {
-        static_for<0, 2>([&](auto hc) {
-            constexpr int h = decltype(hc)::value;
-            u32x4 pv[HP];
-#pragma unroll
-            for (int i = 0; i < HP; ++i) pv[i] = __builtin_bit_cast(u32x4, lds_b128p(piece_addr(buf, HP * h + i)));
-#pragma unroll
-            for (int i = 0; i < HP; ++i) {
-                const uint32_t vm = piece_mask(HP * h + i);
-                u32x4 o;
-                static_for<0, 4>([&](auto qc) { o[decltype(qc)::value] = tpart(pv[i][decltype(qc)::value], qc, vm); });
-                *(lds_u32x4*)(uintptr_t)piece_addr(buf, HP * h + i) = o;
-            }
-        });
-    };
-    if constexpr (FUSE && !IN32 && !FPIPE) {
-        if constexpr (VAR == 3) {                            // the statistics are the oldest requests: their arithmetic runs under the rows' flight
-            asm volatile("s_waitcnt vmcnt(%0)" :: "i"(6 + PXPW + 9) : "memory");
-            stats_landed();
-        }
-        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");     // coefficients and rows of chunk 0
-        coef_landed(0);
-        transform_chunk(0);
+        for (int i = 0; i < PXPW; ++i)
+            if (!((pvalid >> i) & 1u)) *(lds_u32x4z*)(uintptr_t)(lds0 + PXBUF + (wv + 4 * i) * 1024 + l * 16) = u32x4{0u, 0u, 0u, 0u};
     }
     // the rows and the fragments have landed (this wave's; the fused variant's rewritten pieces are in LDS) ...
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -824,8 +678,8 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
     __builtin_amdgcn_s_barrier();                                          // ... every wave's
     asm volatile("" ::: "memory");
     MI_PW_NOW(12);
-    // ---- round 5: the PINNED schedule of the plain bf16 conv (VAR 0 / 1).  The unit timeline of the loop below (tools/pw_timeline.py,
-    //      one wave per SIMD, 512 -> 512 @8x8) read 6 450 cycles per chunk against 4 608 of MFMAs: hipcc sinks each LDS read next to its
+    // ---- round 5: the PINNED schedule of the bf16 MFMA mode (every VAR, bf16 and fp32 input).  The unit timeline of a compiler-scheduled loop
+    //      (tools/pw_timeline.py, one wave per SIMD, 512 -> 512 @8x8) read 6 450 cycles per chunk against 4 608 of MFMAs: hipcc sinks each LDS read next to its
     //      first use and clusters the three fragment requests of a unit between two MFMAs (every unit +50..150 cycles), and the chunk
     //      boundary's vmcnt(0) waited out the fragment requests issued one unit earlier (+600).  Here every MFMA is followed by at most
     //      one side operation and a sched_barrier, as a software pipeline over the row units:
@@ -835,22 +689,16 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
     //        of the step, the next chunk's activation pieces behind them in steps 0 and 1 only -- so step 3's opening wait covers them
     //        and the barrier (before unit BH - 1 of step 3, the first to read the other buffer) needs no vmcnt at all; the fragments
     //        of the next chunk's first step are waited for at the very end of step 3, >= 18 gaps after their request.
-    constexpr bool PIPE = PIPE_;
-    if constexpr (PIPE) {
+    if constexpr (!F32) {
         constexpr int CN = (BH % 3 == 1) ? 4 : 3;            // centre fragment registers in rotation (unit u: C[u % CN])
-        constexpr int WSTR = BH >= 4 ? MI_PW_WSTR : 1;        // a fragment request every WSTR gaps
+        constexpr int WSTR = BH >= 4 ? 2 : 1;                 // a fragment request every WSTR gaps
         constexpr int PG0 = 9 * WSTR;                         // first gap with an activation piece request
         constexpr int PPS = (PXPW + 1) / 2;                   // pieces requested per step (steps 0 and 1)
-        // the four waves leave a barrier in the same cycle and would issue every request in the same gap: wave w starts w * 16 cycles late
-        // (one dwordx4 request occupies the CU's address path for about 16 cycles)
-        auto pw_skew = [&]() { if constexpr (MI_PW_SKEW > 0) for (int i_ = 0; i_ < wv * MI_PW_SKEW; ++i_) asm volatile("s_nop 15"); };
-        pw_skew();
         // the next chunk's pieces through registers (an LDS-DMA request cost the issuing wave 50-100 cycles in the unit timeline, a plain
         // request + ds_write_b128 a fraction of that): batch 0 = the first PPS pieces, requested in step 0 and written in step 2 (in-order
         // returns: they have landed once step 2's fragments have), batch 1 requested in step 1 and written in step 3 before the barrier
-        constexpr bool RST = (MI_PW_RSTAGE != 0 || IN32 || FPIPE) && SPIECE;
         constexpr int RSN = IN32 ? 2 : 1;                      // registers sets per piece: fp32 input = 32 bytes per lane
-        u32x4 RS[2][RST ? PPS : 1][RSN];
+        u32x4 RS[2][PPS][RSN];
         const uint32_t wbase = lds0 + wv * 1024 + l * 16;
         auto rs_load = [&](int ch, auto bc, auto jc) {
             constexpr int b = decltype(bc)::value, j = decltype(jc)::value, i = PPS * b + j;
@@ -904,7 +752,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
                 constexpr uint32_t kx32 = ks * 32, kxn = ((ks + 1) & 3) * 32;
                 const uint32_t bufn = ks == 3 ? xnxt : xcur;                      // where the next step's rows are
                 constexpr int prevp = (ks == 1 || ks == 2) ? ((PXPW - PPS * (ks - 1)) < PPS ? (PXPW - PPS * (ks - 1)) : PPS) : 0;
-                if constexpr (ks > 0 && !(MI_PW_PABL & 4)) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(prevp * (RST ? RSN : 1)) : "memory");
+                if constexpr (ks > 0 && !(MI_PW_PABL & 4)) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(prevp * RSN) : "memory");
                 static_for<0, 9>([&](auto tc) { landed16(WB[cur][decltype(tc)::value]); });
                 auto mm = [&](auto ic, auto tapc, const bf16x8& xf) {
                     constexpr int i = decltype(ic)::value, tp = decltype(tapc)::value;
@@ -916,13 +764,9 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
                     constexpr int g = decltype(gc)::value;
                     if constexpr (g % WSTR == 0 && g / WSTR < 9 && !(MI_PW_PABL & 1)) load_w1(ch, std::integral_constant<int, ks + 1>{}, std::integral_constant<int, g / WSTR>{});
                     if constexpr (!(MI_PW_PABL & 2) && ks < 2 && g >= PG0 && (g - PG0) % 2 == 0 && (g - PG0) / 2 < PPS && PPS * ks + (g - PG0) / 2 < PXPW)
-                    {
-                        if constexpr (RST) rs_load(ch + 1, std::integral_constant<int, ks>{}, std::integral_constant<int, (g - PG0) / 2>{});
-                        else if constexpr (SPIECE) stage_s(ch + 1, std::integral_constant<int, (PPS * ks + (g - PG0) / 2) < PXPW ? (PPS * ks + (g - PG0) / 2) : 0>{});
-                        else stage_x(ch + 1, PPS * ks + (g - PG0) / 2);
-                    }
+                        rs_load(ch + 1, std::integral_constant<int, ks>{}, std::integral_constant<int, (g - PG0) / 2>{});
                     // (register staging: the batch requested two steps ago goes to LDS in the odd gaps 1, 3, ... of steps 2 and 3)
-                    if constexpr (FPIPE) {
+                    if constexpr (FUSE) {
                         // fused: the batch requested two steps ago (PPS pieces) is transformed IN its registers, half pieces at a time so that a
                         // half's coefficients (three ds_read_b128, the same for every piece: a lane keeps its channel slot) are read once per batch:
                         // gap 1: coefficients of half 0; gaps 2 .. 1 + PPS: half 0 of piece 0 .. PPS - 1; then half 1 the same way; then the PPS
@@ -955,7 +799,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
                             }
                         }
                     } else
-                    if constexpr (RST && ks >= 2 && (g & 1) && g / 2 < PPS && PPS * (ks - 2) + g / 2 < PXPW)
+                    if constexpr (ks >= 2 && (g & 1) && g / 2 < PPS && PPS * (ks - 2) + g / 2 < PXPW)
                         rs_store(ch + 1, std::integral_constant<int, ks - 2>{}, std::integral_constant<int, g / 2>{});
                 };
                 // ---- unit 0: rows 0 (output row 0, tap row 0) and BH + 1 (output row BH - 1, tap row 2); it reads row 2 and shifts row 1
@@ -990,7 +834,6 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         if constexpr (!(MI_PW_PABL & 16)) __builtin_amdgcn_s_barrier();
                         asm volatile("" ::: "memory");
-                        pw_skew();
                     }
                     static_for<0, 3 * n>([&](auto jc) {
                         constexpr int j = decltype(jc)::value, kxi = j / n, ky = ky0 + j % n, kx = kxi == 0 ? 1 : kxi == 1 ? 0 : 2;
@@ -1036,127 +879,87 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         }
         asm volatile("" :: "v"(Ac), "v"(Bc), "v"(Al), "v"(Bl), "v"(Ar), "v"(Br));
     } else {
-    XA = lds_b128p(xr[0]); XB = lds_b128p(xr[BH + 1]);
-
-    // One chunk = four 16-channel steps of BH + 1 row units (rows {0, BH + 1}, then 1 .. BH: 6, 6, 9, 9, 6 MFMAs at BH = 4, 6, 6, 6 at
-    // BH = 2; consecutive MFMAs go to different accumulators).  A unit reads the next unit's centre fragment(s); units 0-2 request the
-    // next step's fragments (three taps each; units 0-1 at BH = 2), unit min(3, BH) of the first steps two activation pieces of the next chunk; a step
-    // starts once everything the previous one requested before those pieces has landed.  Chunk boundary (before the last unit of
-    // step 3, whose MFMAs then cover the first reads from the other buffer): every wave has read all it needs of this chunk's rows
-    // and has its pieces of the next chunk's.
-    // Fused variants, bf16 input: coefficients and all pieces of the next chunk are requested in step 0 and transformed as one block at
-    // the chunk boundary (transform_chunk).  fp32 input (fused or not): the raw pieces of the next chunk arrive in the staging area half a
-    // chunk at a time and are converted / transformed by raw_half at the end of step 1 and at the chunk boundary.  The last chunk has no
-    // successor: its (clamped) requests are still issued -- the counted waits assume them -- but nothing is transformed.
-    constexpr int XU = BH < 3 ? BH : 3;                      // the unit that requests activation pieces
-    MI_PW_STAMP(4, 3);                                       // (rewrites slot 3 with the entry time; the new stamp = loop entry)
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const uint32_t xcur = (ch & 1) * PXBUF, xnxt = PXBUF - xcur;
-        static_for<0, 4>([&](auto ksc) {
-            constexpr int ks = decltype(ksc)::value, cur = ks & 1, kx32 = ks * 32;
-            // pieces the previous step requested behind its fragments
-            constexpr int PPS = PT == 256 ? 3 : 2;             // activation pieces a step requests (unit XU)
-            constexpr int prevp = ks == 0 ? 0 : (PXPW - PPS * (ks - 1) >= PPS ? PPS : (PXPW - PPS * (ks - 1) > 0 ? PXPW - PPS * (ks - 1) : 0));
-            // (fused: step 0 requested the coefficients, its fragment parts and pieces, the last piece(s) (unit 2: two DMAs) behind
-            //  everything step 1 needs; fp32 input: the second half chunk's six DMAs are requested at the end of step 1, behind step
-            //  2's fragments)
-            if constexpr (ks > 0 && !(ABL & 32))
-                asm volatile("s_waitcnt vmcnt(%0)" :: "i"((FUSE || IN32) ? ((ks == 1 ? 2 : 0) + ((IN32 && ks == 2) ? 2 * (PXPW / 2) : 0)) : (ABL & 2) ? 0 : prevp) : "memory");
-            static_for<0, 9>([&](auto tc) { landed16(WB[cur][decltype(tc)::value]); });
-            auto mm = [&](auto ic, auto tapc, const bf16x8& xf) {
-                constexpr int i = decltype(ic)::value, tp = decltype(tapc)::value;
-                if constexpr (F32) {
+        // ---- exact-fp32 mode: a compiler-scheduled loop (this mode is bound by the matrix pipe, not by the issue of loads: see F32 above).
+        //      One chunk = four 8-channel steps of BH + 1 row units (rows {0, BH + 1}, then 1 .. BH; consecutive MFMAs go to different
+        //      accumulators).  A unit reads the next unit's centre fragment; the two
+        //      column shifts of a row are made once (pw_shift); units 0 .. NPART - 1 request the next step's fragments, unit min(3, BH) of the
+        //      first steps two activation pieces of the next chunk (LDS-DMA, stage_x); a step starts once everything the previous one requested
+        //      before those pieces has landed.  Chunk boundary (before the last unit of step 3, whose MFMAs then cover the first reads from the
+        //      other buffer): every wave has read all it needs of this chunk's rows and has its pieces of the next chunk's.  The last chunk
+        //      has no successor: its (clamped) requests are still issued -- the counted waits assume them.
+        bf16x8 XA, XB, XP, XQ;                                // centre fragments (16 bytes = 4 fp32 channels): rows 0 and BH + 1 of a step; odd / even rows 1 .. BH
+        XA = lds_b128p(xr[0]); XB = lds_b128p(xr[BH + 1]);
+        constexpr int XU = BH < 3 ? BH : 3;                  // the unit that requests activation pieces
+        constexpr int PPS = 2;                               // ... and how many per step
+        for (int ch = 0; ch < nchunks; ++ch) {
+            const uint32_t xcur = (ch & 1) * PXBUF, xnxt = PXBUF - xcur;
+            static_for<0, 4>([&](auto ksc) {
+                constexpr int ks = decltype(ksc)::value, cur = ks & 1, kx32 = ks * 32;
+                // pieces the previous step requested behind its fragments
+                constexpr int prevp = ks == 0 ? 0 : (PXPW - PPS * (ks - 1) >= PPS ? PPS : (PXPW - PPS * (ks - 1) > 0 ? PXPW - PPS * (ks - 1) : 0));
+                if constexpr (ks > 0) asm volatile("s_waitcnt vmcnt(%0)" :: "i"(prevp) : "memory");
+                static_for<0, 9>([&](auto tc) { landed16(WB[cur][decltype(tc)::value]); });
+                auto mm = [&](auto ic, auto tapc, const bf16x8& xf) {
+                    constexpr int i = decltype(ic)::value, tp = decltype(tapc)::value;
                     const f32x4 wv4 = __builtin_bit_cast(f32x4, WB[cur][tp]), xv4 = __builtin_bit_cast(f32x4, xf);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv4[j], xv4[j], acc[i], 0, 0, 0);
-                } else
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, WB[cur][tp]), xf, acc[i], 0, 0, 0);
-            };
-#define MI_MM(I, KY, KX, XF) mm(std::integral_constant<int, I>{}, std::integral_constant<int, (KY) * 3 + (KX)>{}, XF)
-            auto sh_l = [&](const bf16x8& c) { if constexpr (ABL & 16) return c; else return pw_shift<0>(c, mask_l); };
-            auto sh_r = [&](const bf16x8& c) { if constexpr (ABL & 16) return c; else return pw_shift<1>(c, mask_r); };
-            // what a unit issues besides its MFMAs
-            auto issue = [&](auto uc) {
-                constexpr int u = decltype(uc)::value;
-                if constexpr (IN32 && FUSE && u == 0 && ks == 0) load_coef(ch + 1);      // (the oldest requests of the step)
-                if constexpr (u < NPART && !(ABL & 1)) load_w3(ch, std::integral_constant<int, ks + 1>{}, uc);
-                if constexpr (IN32) {
-                    // the raw fp32 pieces of the next chunk go to the staging area by DMA, half a chunk at a time: the first half's pieces in
-                    // step 0 (one per unit, behind the unit's fragments), the second half's at the end of step 1 (raw_half's caller).
-                    // (Round 4: the plain fp32-input conv too -- it staged two pieces per step through registers with counted waits.)
-                    if constexpr (ks == 0 && u < RHP) stage_raw(ch + 1, u, u);
-                }
-                if constexpr (FUSE && !IN32) {
-                    // Round 4: ALL pieces of the next chunk are requested in step 0 (two per unit, behind the unit's fragments; a DMA
-                    // needs no registers), so a piece has a whole step to arrive before it is read back and transformed -- requested
-                    // one unit before the step that transforms it, every step began by waiting out an HBM round trip.
-                    if constexpr (ks == 0 && u == 0) load_coef(ch + 1);
-                    if constexpr (ks == 0 && 2 * u < PXPW) { stage_x(ch + 1, 2 * u); stage_x(ch + 1, 2 * u + 1); }
-                } else if constexpr (u == XU && !IN32 && PPS * ks < PXPW && !(ABL & 2)) {
-                    static_for<0, PPS>([&](auto pc) { constexpr int pi = PPS * ks + decltype(pc)::value; if constexpr (pi < PXPW) stage_x(ch + 1, pi); });
-                }
-            };
-            // ---- unit 0: rows 0 (output row 0, tap row 0) and BH + 1 (output row BH - 1, tap row 2)
-            {
-                constexpr std::integral_constant<int, 0> U{};
-                MI_PW_STAMP(ks, ch * (BH + 1));
-                XP = lds_b128p((xr[1] ^ kx32) + xcur);
-                issue(U);
-                MI_MM(0, 0, 1, XA); MI_MM(BH - 1, 2, 1, XB);
-                { const bf16x8 la = sh_l(XA), lb = sh_l(XB); MI_MM(0, 0, 0, la); MI_MM(BH - 1, 2, 0, lb); }
-                { const bf16x8 ra = sh_r(XA), rb = sh_r(XB); MI_MM(0, 0, 2, ra); MI_MM(BH - 1, 2, 2, rb); }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // ---- units 1 .. BH: row r feeds output rows r - ky (tap row ky); the last one reads rows 0 and BH + 1 of the next step
-            static_for<1, BH + 1>([&](auto rc) {
-                constexpr int r = decltype(rc)::value;
-                MI_PW_STAMP(ks, ch * (BH + 1) + r);
-                auto& xc = [&]() -> bf16x8& { if constexpr (r & 1) return XP; else return XQ; }();
-                if constexpr (r < BH) {
-                    auto& xn = [&]() -> bf16x8& { if constexpr (r & 1) return XQ; else return XP; }();
-                    xn = lds_b128p((xr[r + 1] ^ kx32) + xcur);
-                } else if constexpr (ks == 3) {
-                    if constexpr (FUSE && !IN32) {
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (requested in step 0)
-                        if (ch + 1 < nchunks) { coef_landed(ch + 1); transform_chunk((ch + 1) & 1); }
-                    }
-                    if constexpr (IN32) {
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (the second half chunk: requested two steps ago)
-                        if (ch + 1 < nchunks) raw_half((ch + 1) & 1, 1);
-                    }
-                    if constexpr (ABL & 32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
-                    XA = lds_b128p(xr[0] + xnxt); XB = lds_b128p(xr[BH + 1] + xnxt);
-                } else {
-                    if constexpr (IN32 && ks == 1) {
-                        // first half chunk (requested in step 0; younger: this step's nine fragment requests), then the second half's
-                        // requests -- the staging slots are free once raw_half has read them
-                        asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-                        if (ch + 1 < nchunks) { if constexpr (FUSE) coef_landed(ch + 1); raw_half((ch + 1) & 1, 0); }
-                        static_for<0, RHP>([&](auto ic) { stage_raw(ch + 1, RHP + decltype(ic)::value, decltype(ic)::value); });
-                    }
-                    XA = lds_b128p((xr[0] ^ (kx32 + 32)) + xcur); XB = lds_b128p((xr[BH + 1] ^ (kx32 + 32)) + xcur);
-                }
-                issue(rc);
-                // (ky, i = r - ky) with 0 <= i < BH, centre column first
-                auto taps = [&](auto kxc, const bf16x8& xf) {
-                    constexpr int kx = decltype(kxc)::value;
-                    static_for<0, 3>([&](auto kyc) {
-                        constexpr int ky = decltype(kyc)::value, i = r - ky;
-                        if constexpr (i >= 0 && i < BH) MI_MM(i, ky, kx, xf);
-                    });
                 };
-                taps(std::integral_constant<int, 1>{}, xc);
-                { const bf16x8 lf = sh_l(xc); taps(std::integral_constant<int, 0>{}, lf); }
-                { const bf16x8 rf = sh_r(xc); taps(std::integral_constant<int, 2>{}, rf); }
-                __builtin_amdgcn_sched_barrier(0);
-            });
+#define MI_MM(I, KY, KX, XF) mm(std::integral_constant<int, I>{}, std::integral_constant<int, (KY) * 3 + (KX)>{}, XF)
+                // what a unit issues besides its MFMAs
+                auto issue = [&](auto uc) {
+                    constexpr int u = decltype(uc)::value;
+                    // (never instantiated: this mode has neither IN32 nor FUSE.  A line of the loop this one was cut from, kept because naming
+                    //  load_coef here decides where hipcc places this loop's fragment requests among the MFMAs -- without it: the same
+                    //  instructions in another order, which nobody has measured.  Goes with the first change that measures this mode.)
+                    if constexpr (IN32 && FUSE && u == 0 && ks == 0) load_coef(ch + 1);
+                    if constexpr (u < NPART) load_w3(ch, std::integral_constant<int, ks + 1>{}, uc);
+                    if constexpr (u == XU && PPS * ks < PXPW)
+                        static_for<0, PPS>([&](auto pc) { constexpr int pi = PPS * ks + decltype(pc)::value; if constexpr (pi < PXPW) stage_x(ch + 1, pi); });
+                };
+                // ---- unit 0: rows 0 (output row 0, tap row 0) and BH + 1 (output row BH - 1, tap row 2)
+                {
+                    constexpr std::integral_constant<int, 0> U{};
+                    XP = lds_b128p((xr[1] ^ kx32) + xcur);
+                    issue(U);
+                    MI_MM(0, 0, 1, XA); MI_MM(BH - 1, 2, 1, XB);
+                    { const bf16x8 la = pw_shift<0>(XA, mask_l), lb = pw_shift<0>(XB, mask_l); MI_MM(0, 0, 0, la); MI_MM(BH - 1, 2, 0, lb); }
+                    { const bf16x8 ra = pw_shift<1>(XA, mask_r), rb = pw_shift<1>(XB, mask_r); MI_MM(0, 0, 2, ra); MI_MM(BH - 1, 2, 2, rb); }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                // ---- units 1 .. BH: row r feeds output rows r - ky (tap row ky); the last one reads rows 0 and BH + 1 of the next step
+                static_for<1, BH + 1>([&](auto rc) {
+                    constexpr int r = decltype(rc)::value;
+                    auto& xc = [&]() -> bf16x8& { if constexpr (r & 1) return XP; else return XQ; }();
+                    if constexpr (r < BH) {
+                        auto& xn = [&]() -> bf16x8& { if constexpr (r & 1) return XQ; else return XP; }();
+                        xn = lds_b128p((xr[r + 1] ^ kx32) + xcur);
+                    } else if constexpr (ks == 3) {
+                        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                        __builtin_amdgcn_s_barrier();
+                        asm volatile("" ::: "memory");
+                        XA = lds_b128p(xr[0] + xnxt); XB = lds_b128p(xr[BH + 1] + xnxt);
+                    } else {
+                        XA = lds_b128p((xr[0] ^ (kx32 + 32)) + xcur); XB = lds_b128p((xr[BH + 1] ^ (kx32 + 32)) + xcur);
+                    }
+                    issue(rc);
+                    // (ky, i = r - ky) with 0 <= i < BH, centre column first
+                    auto taps = [&](auto kxc, const bf16x8& xf) {
+                        constexpr int kx = decltype(kxc)::value;
+                        static_for<0, 3>([&](auto kyc) {
+                            constexpr int ky = decltype(kyc)::value, i = r - ky;
+                            if constexpr (i >= 0 && i < BH) MI_MM(i, ky, kx, xf);
+                        });
+                    };
+                    taps(std::integral_constant<int, 1>{}, xc);
+                    { const bf16x8 lf = pw_shift<0>(xc, mask_l); taps(std::integral_constant<int, 0>{}, lf); }
+                    { const bf16x8 rf = pw_shift<1>(xc, mask_r); taps(std::integral_constant<int, 2>{}, rf); }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
 #undef MI_MM
-        });
+            });
+        }
     }
-    }   // !PIPE
     MI_PW_STAMP(4, 0);                                       // slot 0: the last point's time; new stamp = loop end
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the clamped re-fetches must not outlive the workgroup's LDS ...
     static_for<0, 9>([&](auto tc) { landed16(WB[0][decltype(tc)::value]); landed16(WB[1][decltype(tc)::value]); });   // ... nor their registers
@@ -1203,15 +1006,6 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
             }
         }
     }
-    if constexpr ((ABL & 4) != 0) {
-        float v = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v += acc[i][r];
-        if (v == 123.456f) reinterpret_cast<float*>(a.y)[t] = v;
-        return;
-    }
 
 #ifdef MI_PW_TIMING
     auto ts_out = [&]() {
@@ -1251,21 +1045,6 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         for (int k = 0; k < 4; ++k) {
             r[k] += __shfl_xor(r[k], 1, 64); r[k] += __shfl_xor(r[k], 16, 64); r[k] += __shfl_xor(r[k], 32, 64);
         }
-#if MI_PW_GNSW == 1        // A/B build: every wave adds its own partial sums (no LDS, no barrier; four times the atomics)
-        if ((l & 0x31) == 0) {
-            const int slab = (n0 >> 4) + (l >> 1);
-            if (slab * 16 < a.Nc) {
-                if (a.TI > 1) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) gsum_add(a.gsum, ((size_t)(img0 + (k >> 1)) * (a.Nc >> 4) + slab) * 2 + (k & 1), r[k]);
-                } else {
-                    gsum_add(a.gsum, ((size_t)img0 * (a.Nc >> 4) + slab) * 2, r[0] + r[2]);
-                    gsum_add(a.gsum, ((size_t)img0 * (a.Nc >> 4) + slab) * 2 + 1, r[1] + r[3]);
-                }
-            }
-        }
-        return;
-#endif
         float* red = reinterpret_cast<float*>(lds_raw + PT * 512);        // behind the tile: [4 waves][8 slabs][4]
         if ((l & 0x31) == 0) {
 #pragma unroll
@@ -1290,10 +1069,10 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
     asm volatile("" ::: "memory");
     MI_PW_NOW(13);
     // Round 4: a bf16 output with nothing to add on the way out (no residual, no accumulate -- every forward Block conv and the data
-    // gradients into block-internal tensors) takes its bias in registers and crosses LDS as bf16: half the tile (32 KB), one
+    // gradients into block-internal tensors) takes its bias on the way into LDS and crosses it as bf16: half the tile (32 KB), one
     // ds_read_b128 per thread and pixel, no arithmetic between the read and the store.  8-byte slot c (4 channels) of pixel p at
     // c ^ ((p & 15) << 1): an even XOR keeps a thread's two slots an aligned pair; rows p and p + 16 share banks (2-way on the writes only).
-    const bool tile16 = OUT16 && (!FUSE || FPIPE) && !a.res && !a.accumulate;
+    const bool tile16 = OUT16 && !a.res && !a.accumulate;
     if (tile16) {
         if constexpr (OUT16) {
             typedef __attribute__((address_space(3))) u32x2 lds_u32x2;
@@ -1302,9 +1081,8 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const int ck = 8 * wv + 2 * rq + (l >> 5);
-                    f32x4 bq;
-                    if constexpr (PIPE_) { typedef __attribute__((address_space(3))) f32x4 lds_f32x4b; bq = *(lds_f32x4b*)(uintptr_t)(lds0 + BIASL + 16 * ck); }
-                    else bq = bias_q[rq];
+                    typedef __attribute__((address_space(3))) f32x4 lds_f32x4b;
+                    const f32x4 bq = *(lds_f32x4b*)(uintptr_t)(lds0 + BIASL + 16 * ck);
 #pragma unroll
                     for (int i = 0; i < BH; ++i) {
                         const int p = ep_p0 + i * a.W;
@@ -1429,7 +1207,6 @@ bool pw_ok(const MiConvDesc* d, int pt, int* TH, int* TI, bool in32 = false, boo
 // 64-pixel tiles where 128-pixel ones would leave CUs without a workgroup (and the geometry allows them)
 int g_pw_force_tile = 0;                 // tests: 0 = the rule below, 64 / 128 / 256 = that tile (or unsupported)
 int g_pw_auto256 = 0, g_pw_min256 = 256;   // (measured slower than two 128-pixel workgroups per CU on every cfg-2 shape: off)  // the automatic pick takes 256-pixel tiles when they give at least g_pw_min256 workgroups
-constexpr bool pw_fpipe(bool in32) { return (MI_PW_PIPE != 0) && (((MI_PW_FPIPE) >> (in32 ? 1 : 0)) & 1) != 0; }   // conv_pw_kernel's FPIPE
 // split-K workspace of conv_pw_kernel, per device: [flags: 64 KB of ints, zero when no launch is in flight][fp32 partial tiles].  The caller owns the
 // memory (zeroed once, alive as long as any captured graph may replay); launches that use it must be ordered against each other (one stream).
 std::atomic<void*> g_pw_sk_ws[64];
@@ -1467,7 +1244,7 @@ int pw_split(const MiConvDesc* d, int var, bool in32, int* pt, int* TH, int* TI)
 int pw_pick_tile(const MiConvDesc* d, int var, int* TH, int* TI, bool in32 = false, bool f32 = false, int* ksplit = nullptr) {
     if (ksplit) *ksplit = 1;
     if (f32 && var != 0) return 0;
-    if (var >= 2 && pw_fpipe(in32) && d->K > 1024) return 0;   // the coefficient table of the pinned fused loop: 12 K bytes of LDS
+    if (var >= 2 && d->K > 1024) return 0;   // the coefficient table of the fused variants: 12 K bytes of LDS
     if (!f32 && ksplit) {
         int pts = 0;
         const int ks = pw_split(d, var, in32, &pts, TH, TI);
@@ -2304,42 +2081,15 @@ static int pw_launch(const char* who, const MiConvDesc* d, const void* x, const 
     a.ppx = a.gx / 4; a.cpq = a.gy / 2; a.cpq_magic = pw_magic(a.cpq);
     grid.z = (unsigned)a.ksplit;
     hipStream_t st = (hipStream_t)stream;
-    size_t lds = pw_lds(pt, in32 && !(var >= 2 && pw_fpipe(true)));
-    if (var >= 2 && pw_fpipe(in32)) {                        // the coefficient table sits behind the two activation buffers + 2 KB
+    size_t lds = pw_lds(pt, in32 && var < 2);
+    if (var >= 2) {                                          // the coefficient table sits behind the two activation buffers + 2 KB
         const size_t need = (size_t)2 * pw_xp(pt) * 128 + 2048 + (size_t)12 * d->K;
         if (need > lds) lds = need;
     }
-#define MI_PW_GO_T(O16, V, A, T) do { \
+#define MI_PW_GO_T(O16, V, T) do { \
         static MiPerDevice once_; \
-        once_.run([] { (void)hipFuncSetAttribute((const void*)conv_pw_kernel<O16, V, A, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
-        hipLaunchKernelGGL((conv_pw_kernel<O16, V, A, T>), grid, dim3(256), lds, st, a); } while (0)
-#define MI_PW_GO(O16, V, A) MI_PW_GO_T(O16, V, A, 128)
-#ifdef MI_PW_ABL_BUILD
-    static const int abl = [] { const char* e = getenv("MI_PW_ABL"); return e ? atoi(e) : 0; }();
-    if (abl & 8) lds = 100 * 1024;            // one workgroup per CU
-    if (var == 0 && pt == 64 && (abl & 0x37)) {       // debugging the 64-pixel tiles
-        switch (abl & 0x37) {
-            case 1: MI_PW_GO_T(false, 0, 1, 64); break;
-            case 2: MI_PW_GO_T(false, 0, 2, 64); break;
-            case 3: MI_PW_GO_T(false, 0, 3, 64); break;
-            case 4: MI_PW_GO_T(false, 0, 4, 64); break;
-            default: MI_PW_GO_T(false, 0, 7, 64); break;
-        }
-        hipError_t e_ = hipGetLastError();
-        return e_ == hipSuccess ? 0 : mi_set_error((int)e_, "%s: %s", who, hipGetErrorString(e_));
-    }
-    if (var == 0 && pt == 128 && (abl & 0x37)) {
-#define MI_PW_ABL_CASE(V) case V: if (out_bf16) MI_PW_GO(true, 0, V); else MI_PW_GO(false, 0, V); break;
-        switch (abl & 0x37) {
-            MI_PW_ABL_CASE(1) MI_PW_ABL_CASE(2) MI_PW_ABL_CASE(3) MI_PW_ABL_CASE(4) MI_PW_ABL_CASE(7)
-            MI_PW_ABL_CASE(16) MI_PW_ABL_CASE(17) MI_PW_ABL_CASE(19) MI_PW_ABL_CASE(23) MI_PW_ABL_CASE(32) MI_PW_ABL_CASE(36)
-            default: return mi_set_error(-1, "MI_PW_ABL: combination not built");
-        }
-#undef MI_PW_ABL_CASE
-        hipError_t e_ = hipGetLastError();
-        return e_ == hipSuccess ? 0 : mi_set_error((int)e_, "%s: %s", who, hipGetErrorString(e_));
-    }
-#endif
+        once_.run([] { (void)hipFuncSetAttribute((const void*)conv_pw_kernel<O16, V, 0, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
+        hipLaunchKernelGGL((conv_pw_kernel<O16, V, 0, T>), grid, dim3(256), lds, st, a); } while (0)
 #define MI_PW_GO_X(O16, V, T) do { \
         static MiPerDevice once_; \
         once_.run([] { (void)hipFuncSetAttribute((const void*)conv_pw_kernel<O16, V, 0, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
@@ -2365,20 +2115,19 @@ static int pw_launch(const char* who, const MiConvDesc* d, const void* x, const 
             default: if (out_bf16) MI_PW_GO_X(true, 0, 128); else MI_PW_GO_X(false, 0, 128); break;
         }
     } else if (pt == 256) switch (var) {
-        case 1: if (out_bf16) MI_PW_GO_T(true, 1, 0, 256); else MI_PW_GO_T(false, 1, 0, 256); break;
-        default: if (out_bf16) MI_PW_GO_T(true, 0, 0, 256); else MI_PW_GO_T(false, 0, 0, 256); break;
+        case 1: if (out_bf16) MI_PW_GO_T(true, 1, 256); else MI_PW_GO_T(false, 1, 256); break;
+        default: if (out_bf16) MI_PW_GO_T(true, 0, 256); else MI_PW_GO_T(false, 0, 256); break;
     } else if (pt == 64) switch (var) {
-        case 1: if (out_bf16) MI_PW_GO_T(true, 1, 0, 64); else MI_PW_GO_T(false, 1, 0, 64); break;
-        case 2: if (out_bf16) MI_PW_GO_T(true, 2, 0, 64); else MI_PW_GO_T(false, 2, 0, 64); break;
-        case 3: if (out_bf16) MI_PW_GO_T(true, 3, 0, 64); else MI_PW_GO_T(false, 3, 0, 64); break;
-        default: if (out_bf16) MI_PW_GO_T(true, 0, 0, 64); else MI_PW_GO_T(false, 0, 0, 64); break;
+        case 1: if (out_bf16) MI_PW_GO_T(true, 1, 64); else MI_PW_GO_T(false, 1, 64); break;
+        case 2: if (out_bf16) MI_PW_GO_T(true, 2, 64); else MI_PW_GO_T(false, 2, 64); break;
+        case 3: if (out_bf16) MI_PW_GO_T(true, 3, 64); else MI_PW_GO_T(false, 3, 64); break;
+        default: if (out_bf16) MI_PW_GO_T(true, 0, 64); else MI_PW_GO_T(false, 0, 64); break;
     } else switch (var) {
-        case 1: if (out_bf16) MI_PW_GO(true, 1, 0); else MI_PW_GO(false, 1, 0); break;
-        case 2: if (out_bf16) MI_PW_GO(true, 2, 0); else MI_PW_GO(false, 2, 0); break;
-        case 3: if (out_bf16) MI_PW_GO(true, 3, 0); else MI_PW_GO(false, 3, 0); break;
-        default: if (out_bf16) MI_PW_GO(true, 0, 0); else MI_PW_GO(false, 0, 0); break;
+        case 1: if (out_bf16) MI_PW_GO_T(true, 1, 128); else MI_PW_GO_T(false, 1, 128); break;
+        case 2: if (out_bf16) MI_PW_GO_T(true, 2, 128); else MI_PW_GO_T(false, 2, 128); break;
+        case 3: if (out_bf16) MI_PW_GO_T(true, 3, 128); else MI_PW_GO_T(false, 3, 128); break;
+        default: if (out_bf16) MI_PW_GO_T(true, 0, 128); else MI_PW_GO_T(false, 0, 128); break;
     }
-#undef MI_PW_GO
 #undef MI_PW_GO_T
 #undef MI_PW_GO_X
     hipError_t e_ = hipGetLastError();
