@@ -555,6 +555,12 @@ extern "C" int mi_conv_s2_wgrad_f32(const MiWgradDesc* d, const float* P, const 
     while ((1 << lgh) < d->DH) ++lgh;
     int first[4], count[4];
     const int ng = s2f_groups(d->KH * d->KW, first, count);
+    // every tap group's workspace is checked before the first launch: the second group can need more than the first (9 taps = 5 + 4:
+    // four problems get more k-slices each than five), and a call that is refused must not have added the first group's taps to dW
+    size_t need = 0;
+    for (int g = 0; g < ng; ++g) { const size_t f = s2f_group_ws(d, count[g]); need = f > need ? f : need; }
+    MI_REQUIRE(need == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= need * sizeof(float)),
+               "workspace too small (mi_conv_s2_wgrad_f32_workspace)");
     for (int g = 0; g < ng; ++g) {
         const int n = count[g];
         MiWgradDesc ds[MAXP]; int q32[MAXP]; long wgs[MAXP];
