@@ -92,6 +92,8 @@ class FlatNet(nn.Module):
                 e.logical_view(flat).copy_(torch.empty(e.shape).uniform_(-bound, bound))
             elif e.init == "one":
                 e.logical_view(flat).fill_(1.0)
+            elif e.init == "normal":                             # nn.Embedding: N(0, 1)
+                e.logical_view(flat).copy_(torch.empty(e.shape).normal_())
         object.__setattr__(self, "_gflat", None)
         object.__setattr__(self, "_dirty", 0)
         object.__setattr__(self, "_anchor", torch.zeros(1, requires_grad=True))

@@ -1516,6 +1516,54 @@ def vae_latent_bwd(h, eps, dz, g_kld, g_dev=None):
     return dh
 
 
+# --------------------------------------------------------------------------- cVAE operators (cvae_ops.hip)
+def _labels_i64(labels, like):
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64 and labels.device == like.device):
+        raise RuntimeError("labels: an int64 tensor on the images' HIP device is expected")
+    return labels.contiguous()
+
+
+def cvae_pack_input(x, labels, ncls):
+    """NCHW images + int64 labels [N] -> the encoder's NHWC input [N, H, W, C + ncls] = [image | one-hot label planes], a view of a
+    buffer whose pixel pitch ceil4(C + ncls) is zero in its padding lanes (one launch: no one-hot tensor, no cat)."""
+    _need_gpu(x)
+    B, Cc, H, W = x.shape
+    labels = _labels_i64(labels, x)
+    assert labels.shape == (B,)
+    ld = (Cc + ncls + 3) // 4 * 4
+    x = x.contiguous()
+    y = torch.empty((B, H, W, ld), device=x.device, dtype=torch.float32)
+    check(load_library().mi_cvae_pack_input(B, Cc, H * W, ncls, _p(x), _p(labels), _p(y), ld, _stream()), "mi_cvae_pack_input")
+    return y[..., :Cc + ncls]
+
+
+def cvae_latent_fwd(h, eps, labels, E):
+    """h [N, 2L] = [mu | log_sigma], eps [N, L], E [ncls, L] -> (zc [N, 2L] = [mu + exp(log_sigma) eps | E[labels]], kld scalar).
+    h None: eps holds z and the call only concatenates -> (zc, None)."""
+    _need_gpu(eps)
+    N, L = eps.shape
+    labels = _labels_i64(labels, eps)
+    assert labels.shape == (N,) and E.shape[1] == L and E.is_contiguous() and (h is None or h.shape == (N, 2 * L))
+    eps = eps.float().contiguous()
+    zc = torch.empty((N, 2 * L), device=eps.device, dtype=torch.float32)
+    kld = torch.empty((), device=eps.device, dtype=torch.float32) if h is not None else None
+    check(load_library().mi_cvae_latent_fwd(N, L, E.shape[0], _p(h), h.stride(0) if h is not None else 0, _p(eps), _p(labels), _p(E),
+                                            _p(zc), _p(kld), _stream()), "mi_cvae_latent_fwd")
+    return zc, kld
+
+
+def cvae_latent_bwd(h, eps, labels, dzc, g_kld, dE, g_dev=None):
+    """dh [N, 2L] from dzc [N, 2L] (its first half is dL/dz); dE [ncls, L] += the label-segmented sum of dzc's second half."""
+    N, L2 = h.shape
+    L = L2 // 2
+    labels = _labels_i64(labels, h)
+    assert dzc.shape == (N, L2) and dzc.stride(1) == 1 and dE.shape[1] == L and dE.is_contiguous()
+    dh = torch.empty((N, L2), device=h.device, dtype=torch.float32)
+    check(load_library().mi_cvae_latent_bwd(N, L, dE.shape[0], _p(h), h.stride(0), _p(eps.float().contiguous()), _p(labels), _p(dzc),
+                                            dzc.stride(0), float(g_kld), _p(g_dev), _p(dh), _p(dE), _stream()), "mi_cvae_latent_bwd")
+    return dh
+
+
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)
 def _dense(*ts):
     for t in ts:

@@ -609,6 +609,25 @@ int mi_vae_latent_fwd(int N, int L, const float* h, int ldh, const float* eps, f
 int mi_vae_latent_bwd(int N, int L, const float* h, int ldh, const float* eps, const float* dz, float g_kld, const float* g_dev,
                       float* dh, int lddh, void* stream);
 
+/* ---- cVAE operators (reference src/models/cvae.py; csrc/cvae_ops.hip) ------------------------------------------------------------
+ * Label-indexed data movement of the label-conditioned VAE; labels are int64[N] on the device.  fp32, no atomics: every sum has
+ * a fixed order, so two calls on the same inputs give the same bits.  A label outside [0, ncls) selects nothing (no one-hot
+ * plane, a zero embedding half, no gradient row) and is never used as an index.
+ * mi_cvae_pack_input: NCHW images -> the encoder's NHWC input [N][HW][ld], ld >= C + ncls: channels < C the image, channel C + k
+ *   1 where k == labels[n] else 0, channels >= C + ncls zero (cvae.py:66-69 without the one-hot tensor).  Every element is stored.
+ * mi_cvae_latent_fwd: h = [mu | log_sigma] (rows of ldh >= 2L), E = class_embedding.weight [ncls][L];
+ *   zc[n] = [mu + exp(log_sigma) eps | E[labels[n]]] (dense rows of 2L; the embedding half is a copy), *kld = the KL term of
+ *   mi_vae_latent_fwd, STORED by one workgroup (nullable).  h == null: zc[n] = [eps[n] | E[labels[n]]] -- eps holds z, the decode
+ *   path of forward(z, labels) (cvae.py:43-46); kld must be null then.
+ * mi_cvae_latent_bwd: dzc = dL/dzc (rows of lddzc >= 2L); dh (dense [N][2L]) = what mi_vae_latent_bwd gives for dz = dzc[:, :L];
+ *   dE[c][j] += sum over the rows n with labels[n] == c, in ascending n, of dzc[n][L + j]; rows of dE whose class no row carries
+ *   are neither read nor written. */
+int mi_cvae_pack_input(int N, int C, int HW, int ncls, const float* x_nchw, const int64_t* labels, float* y_nhwc, int ld, void* stream);
+int mi_cvae_latent_fwd(int N, int L, int ncls, const float* h, int ldh, const float* eps, const int64_t* labels, const float* E,
+                       float* zc, float* kld, void* stream);
+int mi_cvae_latent_bwd(int N, int L, int ncls, const float* h, int ldh, const float* eps, const int64_t* labels, const float* dzc,
+                       int lddzc, float g_kld, const float* g_dev, float* dh, float* dE, void* stream);
+
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
 int mi_time_embed(int B, int dim, const int64_t* t, float* out, void* stream);
