@@ -586,7 +586,7 @@ extern "C" int mi_conv_small_cin_bf16_supported(int ks, int N, int H, int W, int
 
 extern "C" int mi_conv_small_cin_fwd_io(int ks, int N, int H, int W, int Cin, int Cout, const float* x, int ldx, const float* w,
                                         const float* bias, void* yv, int ldy, int y_bf16, void* stream) {
-    MI_REQUIRE(x && w && yv && (ks == 1 || ks == 3) && Cin >= 1 && Cin <= 4 && Cout % 4 == 0 && Cout <= 1024 && 256 % (Cout / 4) == 0 &&
+    MI_REQUIRE(x && w && yv && (ks == 1 || ks == 3) && Cin >= 1 && Cin <= 4 && Cout >= 4 && Cout % 4 == 0 && Cout <= 1024 && 256 % (Cout / 4) == 0 &&
                ldy % 4 == 0 && (((uintptr_t)yv & (y_bf16 ? 7 : 15)) | ((uintptr_t)w & 15)) == 0,
                "needs ks 1|3, Cin <= 4, Cout a multiple of 4 with Cout/4 dividing 256, 16-byte aligned y / w");
     float* y = (float*)yv;
@@ -627,7 +627,7 @@ extern "C" int mi_conv_small_cin_fwd_io(int ks, int N, int H, int W, int Cin, in
 // y1 (fp32) = conv1x1(x, w1) + bias1.  Whole-row-tile geometry only (mi_conv_small_cin_fwd_dual_supported).
 extern "C" int mi_conv_small_cin_fwd_dual_supported(int N, int H, int W, int Cin, int Cout, int ldx) {
     static const int tiled = (int)mi_knob("MI_SMALL_CIN_TILED", 1);
-    return (tiled && N > 0 && Cin >= 1 && Cin <= 4 && Cout % 4 == 0 && Cout <= 256 && 256 % (Cout / 4) == 0 && ((long)N * H * W) % 64 == 0 &&
+    return (tiled && N > 0 && Cin >= 1 && Cin <= 4 && Cout >= 4 && Cout % 4 == 0 && Cout <= 256 && 256 % (Cout / 4) == 0 && ((long)N * H * W) % 64 == 0 &&
             cin_tiled_geom(3, H, W, ldx, nullptr)) ? 1 : 0;
 }
 struct CinChores { void* zero; size_t zero_bytes; const float* gsrc; const long long* gidx; float* gdst; int grow, gB; };
@@ -680,7 +680,7 @@ extern "C" int mi_conv_small_cin_wgrad_io(int ks, int N, int H, int W, int Cin, 
     const int na = ks * ks * Cin;
     MI_REQUIRE(x && dyv && dW && (ks == 1 || ks == 3) && Cin >= 1 && Cin <= 4 && (Cout == 64 || Cout == 128 || Cout == 256) && lddy % 4 == 0 &&
                ((uintptr_t)dyv & (dy_bf16 ? 7 : 15)) == 0 && (size_t)3 * na * (Cout / 4) * 16 <= 48 * 1024,
-               "needs ks 1|3, Cin <= 4, Cout in {64, 128, 256} (3x3: {64, 128}), 16-byte aligned dy rows");
+               "needs ks 1|3, Cin <= 4, Cout in {64, 128, 256} with 3 ks ks Cin (Cout / 4) float4 of reduce area <= 48 KiB (3x3: Cin Cout <= 455), 16-byte aligned dy rows");
     const float* dy = (const float*)dyv;
     float* ws = (workspace && ws_bytes >= mi_conv_small_wgrad_workspace(na * Cout)) ? (float*)workspace : nullptr;
     const int w_sh = log2_exact(W), hw_sh = log2_exact(H * W);

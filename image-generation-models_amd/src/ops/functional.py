@@ -679,7 +679,7 @@ def small_cin_supported(ks, Cin, Cout, wgrad=False):
         return False
     if wgrad:
         return Cout in (64, 128, 256) and 3 * ks * ks * Cin * (Cout // 4) * 16 <= 48 * 1024
-    return Cout % 4 == 0 and Cout <= 1024 and 256 % (Cout // 4) == 0
+    return Cout >= 4 and Cout % 4 == 0 and Cout <= 1024 and 256 % (Cout // 4) == 0
 
 
 @functools.lru_cache(maxsize=None)

@@ -253,7 +253,8 @@ int mi_conv1x1_pw(const MiConvDesc* d, const void* x, const void* x2, const void
 /* ---- the 3-channel ends of the UNet (fp32 VALU, bound by the wide tensor they stream) ------------
  * Conv2d(Cin<=4, Cout, ks, padding=ks/2), ks = 3 (downs.0.0.block1, ddpm.py:116,208) or 1 (its res_conv,
  * ddpm.py:134): forward and weight gradient; w / dW in the tap-major layout [ks][ks][Cin][Cout].
- * Forward: Cout % 4 == 0 and Cout/4 divides 256.  Weight gradient: Cout in {64, 128, 256} ({64, 128} for ks = 3);
+ * Forward: Cout % 4 == 0 and Cout/4 divides 256.  Weight gradient: Cout in {64, 128, 256} whose reduce area of
+ * 3 * ks*ks*Cin * (Cout/4) float4 fits 48 KiB (ks = 1: all; ks = 3: Cin * Cout <= 455, so Cin = 1 admits 256, Cin = 4 only 64);
  * with a workspace of mi_conv_small_wgrad_workspace(ks*ks*Cin*Cout) bytes the per-workgroup partial tiles are
  * summed in a fixed order (deterministic), without one they are added with fp32 atomics. */
 int mi_conv_small_cin_fwd(int ks, int N, int H, int W, int Cin, int Cout, const float* x, int ldx, const float* w,
@@ -264,7 +265,8 @@ size_t mi_conv_small_wgrad_workspace(int outputs);
 /* Round 4: the wide (Cout-channel) tensor stored as bf16, like every other block-internal tensor of bf16 mode (the reference keeps
  * c1 = conv(x) and its gradient in fp32, ddpm.py:116-120; x, w, dW stay fp32, the arithmetic is the same fp32 FMA chain, the output
  * is rounded once / dy is widened on load).  y_bf16 / dy_bf16 = 1 needs the whole-row-tile kernels: ks = 3, W a power of two <= 64,
- * H*W a power of two, ldx == 4, 16-byte aligned x, Cout in {64, 128} (256: forward only) -- mi_conv_small_cin_bf16_supported answers for both. */
+ * H*W a power of two, ldx == 4, 16-byte aligned x, Cout in {64, 128, 256} under the weight gradient's 48 KiB rule above (Cin = 1: 256 too; a forward alone
+ * takes any Cout <= 256) -- mi_conv_small_cin_bf16_supported answers for both. */
 int mi_conv_small_cin_bf16_supported(int ks, int N, int H, int W, int Cin, int Cout, int ldx);
 /* round 6, inference -- LinearAttention (reference ddpm.py:146-165) folded into its to_out conv: out = ctx^T q is linear in q, so to_out(out) is a 1x1
    conv of q with per-sample weights W_eff[b] = W_out blockdiag(ctx_h^T).  mi_linattn_fold_fwd: qkv bf16 [B][n][3 * heads * 32], w_out_bf16 = to_out's

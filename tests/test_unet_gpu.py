@@ -217,10 +217,10 @@ def test_tiny_adam5_golden(golden_dir):
         assert float((sd[k].cpu() - _t(g["adam5.final." + k])).abs().max()) < 2e-5, k
 
 
-def _seeded(dim, mults, mode):
+def _seeded(dim, mults, mode, channels=3):
     from src.models.ddpm import Unet
     torch.manual_seed(0)
-    net = Unet(dim=dim, dim_mults=mults, channels=3)
+    net = Unet(dim=dim, dim_mults=mults, channels=channels)
     net.compute_mode = mode
     return net.to(DEV)
 
@@ -641,6 +641,79 @@ def test_cfg3_celeba_shape_vs_oracle(mode, tol, gtol):
     assert rel_err(flat_got, flat_ref) < (1e-4 if mode == "fp32" else 2.6e-2)   # whole gradient; bf16 measured 1.3e-2
     bad = [(k, e) for k, e in errs.items() if e > gtol]
     assert not bad, bad[:8]
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_mnist_shape_vs_oracle(mode):
+    """configs/experiment/ddpm/mnist.yaml's geometry (1 channel, 28x28, hidden 64, mults 2-4): the CIN = 1 / Cs = 1 instantiations and the
+    non-power-of-two pixel decode at 28x28, 14x14 and 7x7 -- forward, L1 loss and every gradient vs the float64 oracle, then one short
+    p_sample_loop through the eager loop and the hipGraph sampler.  fp32: the bounds of test_cfg3_celeba_shape_vs_oracle.  bf16: eps and
+    loss are the project's fixed figures; the whole-gradient bound is twice the distance of the oracle itself evaluated under
+    torch.autocast("cpu", bfloat16) on the same batch (the kernels round at fewer points than autocast does; 2x covers another batch of
+    roundings).  Measured on the MI355X: autocast oracle 9.33e-2, kernels 5.74e-2."""
+    from oracle import ddpm_oracle as O
+    from src.models.ddpm import GaussianDiffusion
+    from src.runtime.sampler import GraphSampler
+    net = _seeded(64, (2, 4), mode, channels=1)
+    g = torch.Generator().manual_seed(13)
+    x = torch.rand(2, 1, 28, 28, generator=g) * 2 - 1
+    t = torch.tensor([0, 999])
+    noise = torch.randn(2, 1, 28, 28, generator=g)
+    p = {k: v.detach().cpu().double().contiguous().clone().requires_grad_(True) for k, v in net.state_dict().items()}
+    tab = O.schedule_tables(1000)
+    ref_loss, ref_eps = O.p_losses(p, tab, x.double(), t, noise.double())
+    ref_loss.backward()
+    names = [k for k, _ in net.named_parameters()]
+    flat_ref = torch.cat([p[k].grad.flatten() for k in names])
+    gd = GaussianDiffusion(net, image_size=(28, 28), channels=1, timesteps=1000).to(DEV)
+    net.eval()
+    with torch.no_grad():
+        eps = net(gd.q_sample(x.to(DEV), t.to(DEV), noise.to(DEV)), t.to(DEV))
+    e_eps = rel_err(eps, ref_eps)
+    net.train()
+    loss = gd.p_losses(x.to(DEV), t.to(DEV), noise.to(DEV))
+    loss.backward()
+    e_loss = abs(float(loss) - float(ref_loss))
+    scale = max(float(v.grad.abs().max()) for v in p.values())
+    errs = {}
+    for k, q in net.named_parameters():
+        r = p[k].grad
+        errs[k] = float((q.grad.cpu() - r).norm()) / (float(r.norm()) + 1e-3 * scale * r.numel() ** 0.5)
+    flat_got = torch.cat([q.grad.detach().cpu().flatten() for _, q in net.named_parameters()])
+    e_grad = rel_err(flat_got, flat_ref)
+    out = dict(eps_rel_l2=e_eps, loss_abs=e_loss, worst_grad_rel_l2=max(errs.values()), worst_grad_key=max(errs, key=errs.get), whole_grad_rel_l2=e_grad)
+    if mode == "fp32":
+        record("mnist_shape_vs_oracle_fp32", **out, bounds={"eps_rel_l2": 1e-4, "worst_grad_rel_l2": 3e-3, "whole_grad_rel_l2": 1e-4})
+        assert e_eps < 1e-4 and e_loss < 3e-5 and e_grad < 1e-4, out
+        bad = [(k, e) for k, e in errs.items() if e > 3e-3]
+        assert not bad, bad[:8]
+    else:
+        p32 = {k: v.detach().cpu().float().contiguous().clone().requires_grad_(True) for k, v in net.state_dict().items()}
+        with torch.autocast("cpu", dtype=torch.bfloat16):
+            ac_loss, _ = O.p_losses(p32, tab, x, t, noise)
+        ac_loss.float().backward()
+        yard = rel_err(torch.cat([p32[k].grad.flatten() for k in names]), flat_ref)
+        record("mnist_shape_vs_oracle_bf16", **out, autocast_oracle_whole_grad_rel_l2=yard,
+               bounds={"eps_rel_l2": BF16_EPS_BUDGET, "loss_abs": 1e-4, "whole_grad_rel_l2": 2 * yard})
+        print(f"mnist bf16: whole gradient rel-L2 kernels {e_grad:.3g}, autocast oracle {yard:.3g}")
+        assert e_eps <= BF16_EPS_BUDGET and e_loss < 1e-4, out
+        assert e_grad <= 2 * yard, (e_grad, yard)
+    # the sampler at this geometry: eager loop and captured graph on the same noise tape
+    net.eval()
+    gs_gd = GaussianDiffusion(net, image_size=(28, 28), channels=1, timesteps=4).to(DEV)
+    shape = (2, 1, 28, 28)
+    torch.manual_seed(1)
+    tape = [torch.randn(shape, device=DEV) for _ in range(5)]
+    it = iter(tape)
+    gs_gd.noise_source = lambda s, d: next(it)
+    eager = gs_gd.p_sample_loop(shape, use_graph=False)
+    it = iter(tape)
+    graph = GraphSampler(gs_gd, shape).run()
+    gs_gd.noise_source = None
+    assert eager.shape == shape and bool(torch.isfinite(eager).all()) and bool(torch.isfinite(graph).all())
+    d = float((graph - eager).abs().max())
+    record(f"mnist_sampler_graph_vs_eager_{mode}", max_abs=d)
+    assert d < 1e-5, d
 
 
 def test_rccl_world1_reducer():
