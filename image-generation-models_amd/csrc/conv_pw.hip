@@ -1038,8 +1038,8 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
         return;
 #endif
         // a 16-channel slab = two neighbouring lanes (j = 2q, 2q + 1) x the 16 row groups t >> 4 (4 per wave): lanes, then waves
-        // through the LDS behind the tile, then ONE atomic pair per slab, image and workgroup (rows 0-63 / 64-127 are the two images
-        // of a TI == 2 tile; with TI == 1 both halves belong to image img0)
+        // through the LDS behind the tile, then ONE atomic pair per slab, image and workgroup (the two halves of the tile's pixels -- gs[it / (PT / 32)] -- are
+        // the two images of a TI == 2 tile, 64 + 64 or 32 + 32 pixels; with TI == 1 both halves belong to image img0)
         float r[4] = {gs[0][0], gs[0][1], gs[1][0], gs[1][1]};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1105,7 +1105,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const float e0 = __uint_as_float(o[q] << 16), e1 = __uint_as_float(o[q] & 0xffff0000u);
-                            gs[PT >= 256 ? 0 : it >> 2][0] += e0 + e1; gs[PT >= 256 ? 0 : it >> 2][1] += e0 * e0 + e1 * e1;
+                            gs[PT >= 256 ? 0 : it / (PT / 32)][0] += e0 + e1; gs[PT >= 256 ? 0 : it / (PT / 32)][1] += e0 * e0 + e1 * e1;
                         }
                     }
                 }
@@ -1162,7 +1162,7 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const float e0 = __uint_as_float(o[q] << 16), e1 = __uint_as_float(o[q] & 0xffff0000u);
-                        gs[PT >= 256 ? 0 : it >> 2][0] += e0 + e1; gs[PT >= 256 ? 0 : it >> 2][1] += e0 * e0 + e1 * e1;
+                        gs[PT >= 256 ? 0 : it / (PT / 32)][0] += e0 + e1; gs[PT >= 256 ? 0 : it / (PT / 32)][1] += e0 * e0 + e1 * e1;
                     }
                 }
             } else {
@@ -1171,8 +1171,8 @@ __global__ __launch_bounds__(256, PT == 256 ? 1 : 2) void conv_pw_kernel(const P
                 *reinterpret_cast<f32x4*>(yp) = v0;
                 *reinterpret_cast<f32x4*>(yp + 4) = v1;
                 if constexpr (GNS) {
-                    gs[PT >= 256 ? 0 : it >> 2][0] += (v0.x + v0.y) + (v0.z + v0.w) + (v1.x + v1.y) + (v1.z + v1.w);
-                    gs[PT >= 256 ? 0 : it >> 2][1] += (v0.x * v0.x + v0.y * v0.y) + (v0.z * v0.z + v0.w * v0.w) + (v1.x * v1.x + v1.y * v1.y) + (v1.z * v1.z + v1.w * v1.w);
+                    gs[PT >= 256 ? 0 : it / (PT / 32)][0] += (v0.x + v0.y) + (v0.z + v0.w) + (v1.x + v1.y) + (v1.z + v1.w);
+                    gs[PT >= 256 ? 0 : it / (PT / 32)][1] += (v0.x * v0.x + v0.y * v0.y) + (v0.z * v0.z + v0.w * v0.w) + (v1.x * v1.x + v1.y * v1.y) + (v1.z * v1.z + v1.w * v1.w);
                 }
             }
         }
@@ -2049,7 +2049,7 @@ static int pw_launch(const char* who, const MiConvDesc* d, const void* x, const 
     if (var == 2 && (!coef || ((uintptr_t)coef & 15)))
         return mi_set_error(-1, "%s: the fused variant needs a 16-byte aligned coefficient tensor", who);
     if (var == 3) {
-        if (!gn || !gn->sums || !gn->gamma || !gn->beta || gn->G <= 0 || d->K % gn->G || (d->K / gn->G) % 16 || d->K / gn->G > 64)
+        if (!gn || !gn->sums || !gn->gamma || !gn->beta || gn->G <= 0 || d->K % gn->G || (d->K / gn->G) % 16 || d->K / gn->G > 64 || d->K / gn->G == 48)
             return mi_set_error(-1, "%s: sums, gamma, beta; K / G in {16, 32, 64}", who);
         if ((((uintptr_t)gn->gamma | (uintptr_t)gn->beta | (uintptr_t)gn->sums) & 7) || ((uintptr_t)gn->sums & 15) || (gn->temb && (((uintptr_t)gn->temb & 15) || gn->ldt % 4)))
             return mi_set_error(-1, "%s: misaligned GroupNorm operands", who);
