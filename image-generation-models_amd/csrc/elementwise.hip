@@ -338,6 +338,24 @@ __global__ __launch_bounds__(256) void rowsum_batch_kernel(const RowSumArgs a) {
     if (rl == 0 && c < it.cols) atomicAdd(it.dst + c, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
 }
 
+// base[off .. off + cnt) = 0 for every (off, cnt) pair of a device-resident table: the pieces of a flat gradient buffer that are
+// accumulated into (biases, norm parameters, small layers) between the weight gradients that are written outright.  grid = (ZR_X,
+// ranges); a range is short (a few KB to a few hundred KB): scalar stores up to a 16-byte boundary, float4 stores, a scalar tail.
+constexpr int ZR_X = 8;
+__global__ __launch_bounds__(256) void zero_ranges_kernel(const long long* __restrict__ table, float* __restrict__ base) {
+    const long long off = table[2 * blockIdx.y], cnt = table[2 * blockIdx.y + 1];
+    if (cnt <= 0) return;
+    float* p = base + off;
+    const long long lead = (4 - (long long)(((uintptr_t)p >> 2) & 3)) & 3;
+    const long long head = lead < cnt ? lead : cnt;
+    const long long nv = (cnt - head) >> 2, tail0 = head + 4 * nv;
+    const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (tid < head) p[tid] = 0.f;
+    float4* v = reinterpret_cast<float4*>(p + head);
+    for (long long i = tid; i < nv; i += ZR_X * 256) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tid < cnt - tail0) p[tail0 + tid] = 0.f;
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -424,6 +442,14 @@ extern "C" int mi_rowsum_batch(int n, const MiRowSum* items, void* stream) {
     }
     a.first[n] = tot;
     hipLaunchKernelGGL(rowsum_batch_kernel, dim3(tot), dim3(256), 0, ST, a);
+    MI_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mi_zero_ranges(const long long* table_dev, int n, float* base, void* stream) {
+    MI_REQUIRE(table_dev && base && n >= 1 && n <= 65535 && ((uintptr_t)base & 3) == 0 && ((uintptr_t)table_dev & 7) == 0,
+               "1 .. 65535 ranges, a device table of (offset, count) int64 pairs, a float-aligned base");
+    hipLaunchKernelGGL(zero_ranges_kernel, dim3(ZR_X, (unsigned)n), dim3(256), 0, ST, table_dev, base);
     MI_LAUNCH_CHECK();
     return 0;
 }

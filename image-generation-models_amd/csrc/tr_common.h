@@ -26,6 +26,7 @@ struct TrArgs {
     int wg0;            // first workgroup of this problem in the launch
     int tile0;          // first tile of this problem in the reduce launch
     int xcd_map;        // workgroup -> (k-slice, tile) such that the tiles of a k-slice share an XCD
+    int store;          // != 0: dW = result instead of dW += result (MI_WGRAD_STORE)
 };
 constexpr int MAXP = 8;
 // One launch = up to MAXP independent weight-gradient problems, each on its own share of the workgroups.  A layer's partial-tile
@@ -53,6 +54,12 @@ inline void balance_shares(int n, const double* work, const long* tiles, long ta
         if (worst < top) break;
         wgs[best] += tiles[best]; total += tiles[best];
     }
+}
+
+// One element of dW: added to, or (MI_WGRAD_STORE) written -- the element has no other writer in the call
+__device__ __forceinline__ void wg_put(float* e, float v, int store) {
+    if (store) *e = v;
+    else *e += v;
 }
 
 // LDS-DMA: 16 bytes per lane from each lane's own global address to LDS byte address lds_dst (wave-uniform) + 16 * lane.

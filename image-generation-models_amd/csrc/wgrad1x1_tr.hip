@@ -23,6 +23,7 @@ struct W1Args {
     float* ws; float* dW; float* dbias;
     int Ci, Cj, I1, ldp, ldp2, ldq, q32, ni, f32;
     int total, sps, splits, gx, gy, wg0, tile0, xcd_map;
+    int store;          // != 0: dW = result instead of dW += result (MI_WGRAD_STORE); dbias is always added
     // round 6, exact-fp32 mode only: ONE TAP of a stride-2 / transposed conv's weight gradient as a gathered 1x1 problem -- the pixels m of the
     // small (dense) grid [N][1 << (lghw - lgw)][1 << lgw] meet pixel (2 y + gdy, 2 x + gdx) of the big [N][GH][GW] tensor (zero outside)
     int gmode;          // 0: plain 1x1; 1: P is the big (gathered) tensor; 2: Q is
@@ -159,7 +160,7 @@ __device__ __forceinline__ void wgrad1_body(const W1Args& a, const int wg, uint8
             if (co < a.Cj) {
                 float* o = a.dW + (size_t)ci * a.Cj + co;
 #pragma unroll
-                for (int q = 0; q < 16; ++q) o[(size_t)((q & 3) + 8 * (q >> 2)) * a.Cj] += acc[r][q];
+                for (int q = 0; q < 16; ++q) wg_put(o + (size_t)((q & 3) + 8 * (q >> 2)) * a.Cj, acc[r][q], a.store);
             }
         }
         return;
@@ -274,7 +275,7 @@ __device__ __forceinline__ void wgrad1_f32_body(const W1Args& a, const int wg, u
         if (co < a.Cj) {
             float* o = a.dW + (size_t)ci * a.Cj + co;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) o[(size_t)((q & 3) + 8 * (q >> 2)) * a.Cj] += acc[q];
+            for (int q = 0; q < 16; ++q) wg_put(o + (size_t)((q & 3) + 8 * (q >> 2)) * a.Cj, acc[q], a.store);
         }
         return;
     }
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x1_tr_kernel(const W1Batch b) {
     else           { if (a.q32) wgrad1_body<true, 1>(a, wg, lds_raw); else wgrad1_body<false, 1>(a, wg, lds_raw); }
 }
 
-// dW[ci][co] += sum over k-slices (fixed order); grid = ((512 / IB) position groups x 64-channel regions, 4 register quads, tiles with
+// dW[ci][co] += (store mode: =) sum over k-slices (fixed order); grid = ((512 / IB) position groups x 64-channel regions, 4 register quads, tiles with
 // k-slices), 256 threads = G slice groups x IB = 256 / G float4 positions; each thread keeps 8 independent 16-byte loads in flight.
 // (Round 4: it was 2 slice groups with 2 loads in flight -- a chain of 16 L2 round trips for the 64 k-slices of a to_qkv layer, 15 us per
 // launch and six launches per step.)
@@ -358,7 +359,7 @@ __global__ __launch_bounds__(256) void wgrad1x1_tr_reduce_kernel(const W1Batch b
     float* out = a.dW + (size_t)ci * a.Cj + co;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        if (ci + e < a.Ci) out[(size_t)e * a.Cj] += s[e];
+        if (ci + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
 }
 
 bool w1_ok(const MiWgradDesc* d, int q32) {
@@ -449,10 +450,11 @@ extern "C" int mi_debug_wgrad1x1_tr_phase(int phase) {
 }
 extern "C" int mi_debug_wgrad1x1_tr_blocks(int blocks) { g_w1_blocks = blocks > 0 ? blocks : 0; return 0; }
 
-extern "C" int mi_conv1x1_wgrad_tr_batch(int n, const MiWgradDesc* descs, const int* q_is_fp32, const void* const* P,
-                                         const void* const* P2, const void* const* Q, float* const* dW, float* const* dbias,
-                                         void* workspace, size_t ws_bytes, void* stream) {
+extern "C" int mi_conv1x1_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, const int* q_is_fp32, const void* const* P,
+                                            const void* const* P2, const void* const* Q, float* const* dW, float* const* dbias,
+                                            void* workspace, size_t ws_bytes, void* stream, unsigned flags) {
     MI_REQUIRE(n >= 1 && n <= MAXP && descs && q_is_fp32 && P && Q && dW, "1..8 problems, non-null arrays");
+    MI_REQUIRE((flags & ~MI_WGRAD_STORE) == 0, "unknown flag bit");
     W1Batch b{};                                          // (every field a kernel reads is defined: gmode = 0 means no gather)
     b.n = n;
     long wgs[MAXP];
@@ -472,6 +474,7 @@ extern "C" int mi_conv1x1_wgrad_tr_batch(int n, const MiWgradDesc* descs, const 
         w1_plan(&descs[i], a, wgs[i]);
         a.P = (const uint16_t*)P[i]; a.P2 = (const uint16_t*)((P2 && P2[i]) ? P2[i] : P[i]); a.Q = Q[i];
         a.dW = dW[i]; a.dbias = dbias ? dbias[i] : nullptr; a.q32 = q_is_fp32[i] ? 1 : 0; a.f32 = descs[i].mode == 0 ? 1 : 0;
+        a.store = (flags & MI_WGRAD_STORE) ? 1 : 0;
         a.ldp = descs[i].ldp; a.ldp2 = (P2 && P2[i]) ? descs[i].ldp2 : descs[i].ldp; a.ldq = descs[i].ldq;
         a.ws = (float*)workspace + off;
         off += w1_ws_floats(a);
@@ -499,6 +502,12 @@ extern "C" int mi_conv1x1_wgrad_tr_batch(int n, const MiWgradDesc* descs, const 
     }
     MI_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int mi_conv1x1_wgrad_tr_batch(int n, const MiWgradDesc* descs, const int* q_is_fp32, const void* const* P,
+                                         const void* const* P2, const void* const* Q, float* const* dW, float* const* dbias,
+                                         void* workspace, size_t ws_bytes, void* stream) {
+    return mi_conv1x1_wgrad_tr_batch_ex(n, descs, q_is_fp32, P, P2, Q, dW, dbias, workspace, ws_bytes, stream, 0u);
 }
 
 // ---- round 6, exact-fp32 mode: the weight gradients of Downsample = Conv2d(C, C, 3, 2, 1) and Upsample = ConvTranspose2d(C, C, 4, 2, 1)

@@ -32,6 +32,7 @@ struct S2Args {
     int total, sps, splits;                 // steps of 64 small pixels, steps per k-slice, k-slices
     int gx, gy, ntiles;                     // big-channel tiles (64), small-channel tiles (128), tiles incl. the plane factor
     int wg0, tile0, xcd_map;
+    int store;                              // != 0: dW = result instead of dW += result (MI_WGRAD_STORE)
 };
 struct S2Batch { S2Args p[MAXP]; int n; };
 
@@ -237,7 +238,7 @@ __device__ __forceinline__ void wgrad_s2_body(const S2Args& a, const int wg, uin
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rr = (r & 3) + 8 * (r >> 2);
-                if (ok_col && (!SWAP || row0 + rr < a.Cs)) o[(size_t)rr * a.Cj] += acc[ta][r];
+                if (ok_col && (!SWAP || row0 + rr < a.Cs)) wg_put(o + (size_t)rr * a.Cj, acc[ta][r], a.store);
             }
         }
         return;
@@ -275,7 +276,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_s2_tr_kernel(const S2Batch b) {
     }
 }
 
-// dW += sum over k-slices of the partial tiles (fixed order).  grid = (position groups, slots of the largest problem, tiles of all
+// dW += (store mode: =) sum over k-slices of the partial tiles (fixed order).  grid = (position groups, slots of the largest problem, tiles of all
 // problems that have k-slices); a workgroup = G slice groups x (256 / G) float4 positions of one slot.
 template <int G>
 __global__ __launch_bounds__(256) void wgrad_s2_reduce_kernel(const S2Batch b) {
@@ -323,7 +324,7 @@ __global__ __launch_bounds__(256) void wgrad_s2_reduce_kernel(const S2Batch b) {
     float* out = a.dW + ((size_t)tap * a.Ci + row) * a.Cj + col;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        if (row + e < a.Ci) out[(size_t)e * a.Cj] += s[e];
+        if (row + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
 }
 
 bool s2_ok(const MiWgradDesc* d) {
@@ -412,9 +413,10 @@ extern "C" int mi_debug_wgrad_s2_tr_phase(int phase) {
     return 0;
 }
 
-extern "C" int mi_conv_s2_wgrad_tr_batch(int n, const MiWgradDesc* descs, const void* const* P, const void* const* Q,
-                                         float* const* dW, void* workspace, size_t ws_bytes, void* stream) {
+extern "C" int mi_conv_s2_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, const void* const* P, const void* const* Q,
+                                            float* const* dW, void* workspace, size_t ws_bytes, void* stream, unsigned flags) {
     MI_REQUIRE(n >= 1 && n <= MAXP && descs && P && Q && dW, "1..8 problems, non-null arrays");
+    MI_REQUIRE((flags & ~MI_WGRAD_STORE) == 0, "unknown flag bit");
     S2Batch b;
     b.n = n;
     long wgs[MAXP];
@@ -431,7 +433,7 @@ extern "C" int mi_conv_s2_wgrad_tr_batch(int n, const MiWgradDesc* descs, const 
         s2_plan(&descs[i], a, wgs[i]);
         a.B = (const uint16_t*)(descs[i].gather_i ? P[i] : Q[i]);
         a.S = (const uint16_t*)(descs[i].gather_i ? Q[i] : P[i]);
-        a.dW = dW[i];
+        a.dW = dW[i]; a.store = (flags & MI_WGRAD_STORE) ? 1 : 0;
         a.ws = (float*)workspace + off;
         off += s2_ws_floats(a);
         static const int xcd_env = (int)mi_knob("MI_WS2_XCD", 1);
@@ -455,4 +457,9 @@ extern "C" int mi_conv_s2_wgrad_tr_batch(int n, const MiWgradDesc* descs, const 
     }
     MI_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int mi_conv_s2_wgrad_tr_batch(int n, const MiWgradDesc* descs, const void* const* P, const void* const* Q,
+                                         float* const* dW, void* workspace, size_t ws_bytes, void* stream) {
+    return mi_conv_s2_wgrad_tr_batch_ex(n, descs, P, Q, dW, workspace, ws_bytes, stream, 0u);
 }

@@ -252,14 +252,14 @@ __device__ __forceinline__ void wgrad_tr_body(const TrArgs& a, const int wg, uin
     }
 #endif
     if (a.splits == 1) {
-        // the only k-slice of its tile: add into dW (lanes 0-31 = 32 consecutive co: 128-byte row segments)
+        // the only k-slice of its tile: add into (store mode: write) dW (lanes 0-31 = 32 consecutive co: 128-byte row segments)
         const int ci = ci0 + wi * 32 + 4 * (l >> 5), co = co0 + wj * 32 + (l & 31);
         if (co < a.Cj) {
 #pragma unroll
             for (int tp = 0; tp < 9; ++tp) {
                 float* o = a.dW + ((size_t)tp * a.Ci + ci) * a.Cj + co;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o[(size_t)((r & 3) + 8 * (r >> 2)) * a.Cj] += acc[tp][r];
+                for (int r = 0; r < 16; ++r) wg_put(o + (size_t)((r & 3) + 8 * (r >> 2)) * a.Cj, acc[tp][r], a.store);
             }
         }
         return;
@@ -433,7 +433,7 @@ __device__ __forceinline__ void wgrad_tr32_body(const TrArgs& a, const int wg, u
             for (int tp = 0; tp < 9; ++tp) {
                 float* o = a.dW + ((size_t)tp * a.Ci + ci) * a.Cj + co;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o[(size_t)((r & 3) + 8 * (r >> 2)) * a.Cj] += acc[tp][r];
+                for (int r = 0; r < 16; ++r) wg_put(o + (size_t)((r & 3) + 8 * (r >> 2)) * a.Cj, acc[tp][r], a.store);
             }
         }
         return;
@@ -464,7 +464,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_tr32_kernel(const TrBatch b) {
     }
 }
 
-// dW[tap][ci][co] += sum over k-slices of the partial tiles (fixed order).  grid = (2G position groups, 36 slots, tiles of all
+// dW[tap][ci][co] += (store mode: =) sum over k-slices of the partial tiles (fixed order).  grid = (2G position groups, 36 slots, tiles of all
 // problems that have k-slices); a workgroup = G slice groups x (256 / G) float4 positions of one slot; each thread keeps 8
 // independent 16-byte loads in flight.
 template <int G>
@@ -506,7 +506,7 @@ __global__ __launch_bounds__(256) void wgrad_tr_reduce_kernel(const TrBatch b) {
     float* out = a.dW + ((size_t)tap * a.Ci + ci) * a.Cj + co;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        if (ci + e < a.Ci) out[(size_t)e * a.Cj] += s[e];
+        if (ci + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
 }
 
 bool tr_ok(const MiWgradDesc* d) {
@@ -599,9 +599,11 @@ extern "C" int mi_debug_wgrad_tr_phase(int phase) {
     return 0;
 }
 
-extern "C" int mi_conv3x3_wgrad_tr_batch(int n, const MiWgradDesc* descs, const void* const* P, const void* const* P2,
-                                         const void* const* Q, float* const* dW, void* workspace, size_t ws_bytes, void* stream) {
+extern "C" int mi_conv3x3_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, const void* const* P, const void* const* P2,
+                                            const void* const* Q, float* const* dW, void* workspace, size_t ws_bytes, void* stream,
+                                            unsigned flags) {
     MI_REQUIRE(n >= 1 && n <= MAXP && descs && P && Q && dW, "1..8 problems, non-null arrays");
+    MI_REQUIRE((flags & ~MI_WGRAD_STORE) == 0, "unknown flag bit");
     TrBatch b;
     b.n = n;
     long wgs[MAXP];
@@ -619,7 +621,7 @@ extern "C" int mi_conv3x3_wgrad_tr_batch(int n, const MiWgradDesc* descs, const 
         TrArgs& a = b.p[i];
         tr_plan(&descs[i], a, wgs[i]);
         a.P = (const uint16_t*)P[i]; a.P2 = (const uint16_t*)((P2 && P2[i]) ? P2[i] : P[i]); a.Q = (const uint16_t*)Q[i];
-        a.dW = dW[i];
+        a.dW = dW[i]; a.store = (flags & MI_WGRAD_STORE) ? 1 : 0;
         a.ldp = descs[i].ldp; a.ldp2 = (P2 && P2[i]) ? descs[i].ldp2 : descs[i].ldp; a.ldq = descs[i].ldq;
         a.ws = (float*)workspace + off;
         off += tr_ws_floats(a);
@@ -661,6 +663,11 @@ extern "C" int mi_conv3x3_wgrad_tr_batch(int n, const MiWgradDesc* descs, const 
     }
     MI_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int mi_conv3x3_wgrad_tr_batch(int n, const MiWgradDesc* descs, const void* const* P, const void* const* P2,
+                                         const void* const* Q, float* const* dW, void* workspace, size_t ws_bytes, void* stream) {
+    return mi_conv3x3_wgrad_tr_batch_ex(n, descs, P, P2, Q, dW, workspace, ws_bytes, stream, 0u);
 }
 
 extern "C" int mi_conv3x3_wgrad_tr(const MiWgradDesc* d, const void* P, const void* P2, const void* Q, float* dW,

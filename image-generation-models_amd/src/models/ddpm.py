@@ -281,6 +281,8 @@ class Unet(nn.Module):
         self.fold_attn = K.debug_knob("MI_DDPM_FOLD_ATTN", "0") == "1"
         self.small_cout_bwd1 = K.debug_knob("MI_DDPM_COUT_BWD1", "1") != "0"    # the C -> 3 conv's weight and data gradient in one launch
         self.fuse_final = K.debug_knob("MI_DDPM_FUSE_FINAL", "1") != "0"        # inference: final_conv.0's GroupNorm + Mish inside final_conv.1's load
+        # backward WRITES the conv weights' gradients (MI_WGRAD_STORE) and zero-fills only the rest of flat_grads; 0: fill everything, add
+        self.grad_store = K.debug_knob("MI_DDPM_GRAD_STORE", "1") != "0"
         self.accumulate_grads = False
         self.grad_ready_hook = None        # callable(lo, hi): flat_grads[lo:hi) is final (set by the DDP reducer)
 
@@ -303,6 +305,8 @@ class Unet(nn.Module):
         object.__setattr__(self, "_shadow_key", None)
         object.__setattr__(self, "_shadow32", None)
         object.__setattr__(self, "_shadow32_key", None)
+        object.__setattr__(self, "_zero_tab", None)             # store mode's zero table (_build_zero_table)
+        object.__setattr__(self, "_zero_tab_retired", [])
         object.__setattr__(self, "_anchor", torch.zeros(1, requires_grad=True))
         # module tree in the reference's registration order (time_mlp, downs, ups, mid_*, final_conv)
         self._plist: List[Tuple[_Entry, nn.Parameter]] = []
@@ -403,7 +407,33 @@ class Unet(nn.Module):
                 p.grad = e.logical_view(g)
                 gv[e.key] = e.storage_view(g)
             object.__setattr__(self, "_gv", gv)
+            self._build_zero_table(g.device)
         return self._gflat
+
+    def _build_zero_table(self, device):
+        """The ranges of flat_grads a backward pass in store mode still zero-fills, as a device table of (offset, count) int64 pairs:
+        everything (alignment gaps included) but the weights of the convs and transposed convs with Ci % 64 == 0 and Cj >= 32, which the
+        LDS-DMA weight-gradient kernels write outright; adjacent ranges are one range.  Built together with flat_grads (never inside a
+        backward pass, which may be under graph capture); the table of an earlier device is retired, not freed: a captured graph may
+        still read it.  (A left-out weight that is routed to a kernel that can only add is filled at that point: conv_bwd.)"""
+        skip = []
+        for e in self._arch.entries:
+            if e.layout in ("conv", "convT"):
+                kh, kw, ci, co = e.storage_view(self._flat).shape
+                if ci % 64 == 0 and co >= 32:
+                    skip.append((e.offset, e.numel, e.key))
+        skip.sort()
+        ranges, pos = [], 0
+        for off, numel, _ in skip:
+            if off > pos:
+                ranges.append((pos, off - pos))
+            pos = off + numel
+        if self._arch.flat_numel > pos:
+            ranges.append((pos, self._arch.flat_numel - pos))
+        if self._zero_tab is not None:
+            self._zero_tab_retired.append(self._zero_tab)
+        table = torch.tensor(ranges, dtype=torch.int64).reshape(-1, 2).to(device)
+        object.__setattr__(self, "_zero_tab", (table, len(ranges), frozenset(k for _, _, k in skip)))
 
     def zero_grad(self, set_to_none: bool = False):
         if self._gflat is not None:
@@ -803,7 +833,15 @@ class Unet(nn.Module):
         """Replays the tape in reverse.  d_eps: NHWC gradient of the eps prediction."""
         A, sv, mode = self._arch, self._sv, _mode_id(self.compute_mode)
         gflat = self.flat_grads
-        if not self.accumulate_grads:
+        # store mode: the big conv weights' gradients have one writer each, which writes instead of adding; only the rest (biases, norm
+        # parameters, the time MLP, the 3-channel ends: everything that is accumulated atomically) is zero-filled, in one launch
+        store = self.grad_store and not self.accumulate_grads
+        unfilled = frozenset()
+        if store:
+            table, nranges, unfilled = self._zero_tab
+            if nranges:
+                K.zero_ranges(table, nranges, gflat)
+        elif not self.accumulate_grads:
             gflat.zero_()                                  # wgrad / norm kernels accumulate atomically
         gv = self._gv
         offs = self._offs
@@ -815,7 +853,7 @@ class Unet(nn.Module):
         # data parallel (a grad-ready hook is set): the two Upsample layers come early in backward, the two Downsample layers last; with
         # all four in one launch at the very end their 8 MB of gradients would be all-reduced after backward, exposed -- two per launch
         wq = K.WgradQueue(group=int(K.debug_knob("MI_DDPM_WGRAD_GROUP", "8")),
-                          group_s2=2 if self.grad_ready_hook is not None else None)
+                          group_s2=2 if self.grad_ready_hook is not None else None, store=store)
         x_in = tape[-1][1]
         B = x_in.shape[0]
         # (every column is WRITTEN by its block's GroupNorm backward -- one workgroup per (sample, channel) stores its sum -- before the time MLP's
@@ -847,8 +885,17 @@ class Unet(nn.Module):
             winp = inp if winp is None else winp
             wx2 = x2 if wx2 is None else wx2
             dy16 = None
+            prefill = (pre + "weight") in unfilled       # store mode left this weight's gradient unfilled: only the queue's kernels write
+            filled = [not prefill]
+
+            def fill():
+                """before a kernel that can only add (once per layer)"""
+                if not filled[0]:
+                    gv[pre + "weight"].zero_()
+                    filled[0] = True
             if (x2 is None and stride == 1 and not transposed_conv and k == 1 and K.small_cout_supported(2, ci, co)
                     and K.small_cout_supported(1, ci, co)):
+                fill()
                 if want_dx and self.small_cout_bwd1 and ci in (64, 128, 256):
                     buf, acc = G.target(inp)                      # weight gradient and data gradient from one pass over (inp, dy)
                     K.conv1x1_small_cout_bwd(inp, dy, w, gv[pre + "weight"], buf, accumulate=acc)
@@ -862,7 +909,10 @@ class Unet(nn.Module):
                     K.conv1x1_small_cout(1, dy, w, out=buf, accumulate=acc)
                 return
             small_cin = x2 is None and stride == 1 and not transposed_conv and K.small_cin_supported(k, ci, co, wgrad=True)
+            if stride == 2 and mode == K.MODE_FP32:
+                fill()                  # fp32 mode's stride-2 kernels (the gathered taps, or conv_wgrad when they decline) only add
             if small_cin:
+                fill()
                 K.conv_small_cin_wgrad(inp, dy, gv[pre + "weight"], k)
             elif (stride == 2 and mode == K.MODE_BF16 and self.s2_wgrad_tr and
                   (dy16 := s2_push(dy, winp, pre, kh, ci, co, transposed_conv, (ih, iw), (oh, ow), bias)) is not None):
@@ -872,20 +922,21 @@ class Unet(nn.Module):
                                       grid_g=(oh, ow) if transposed_conv else (ih, iw), grid_d=(ih, iw) if transposed_conv else (oh, ow))):
                 pass                    # fp32 mode (round 6): Downsample / Upsample as gathered 1x1 problems of the exact-fp32 kernel (bias: column sum below)
             elif transposed_conv:   # dW[tap][ci][co] = sum over input pixels  x[j] * dy[gather(j, tap)]
+                fill()
                 K.conv_wgrad(inp, dy, gv[pre + "weight"], kh=kh, kw=kw, stride=stride, pad=pad, gather_i=False,
                              Ci=ci, Cj=co, grid_g=(oh, ow), grid_d=(ih, iw), mode=mode)
             elif k == 3 and stride == 1 and bias != "colsum" and mode == K.MODE_BF16:
                 # Block conv: deferred, several layers per launch (K.WgradQueue)
-                wq.push(winp, dy, gv[pre + "weight"], Ci=ci, Cj=co, hw=(ih, iw), mode=mode, P2=wx2)
+                wq.push(winp, dy, gv[pre + "weight"], Ci=ci, Cj=co, hw=(ih, iw), mode=mode, P2=wx2, prefill=prefill)
             elif (k == 3 and stride == 1 and not transposed_conv and mode == K.MODE_FP32 and winp.dtype == torch.float32
                   and dy.dtype == torch.float32 and ci % 64 == 0):
                 # fp32 mode: the same queue, the exact-fp32 instantiation of the kernel (the bias gradient stays a column sum below)
-                wq.push(winp, dy, gv[pre + "weight"], Ci=ci, Cj=co, hw=(ih, iw), mode=mode, P2=wx2)
+                wq.push(winp, dy, gv[pre + "weight"], Ci=ci, Cj=co, hw=(ih, iw), mode=mode, P2=wx2, prefill=prefill)
             elif k == 1 and stride == 1 and mode == K.MODE_BF16 and winp.dtype == torch.bfloat16:
                 # to_qkv / to_out / res_conv: deferred too; the bias gradient rides along when dy is the fp32 stream gradient
                 fuse_b = bias == "colsum" and dy.dtype == torch.float32
                 wq.push1x1(winp, dy, gv[pre + "weight"], Ci=ci, Cj=co, hw=(ih, iw), mode=mode, P2=wx2,
-                           dbias=gv[pre + "bias"] if fuse_b else None)
+                           dbias=gv[pre + "bias"] if fuse_b else None, prefill=prefill)
                 if fuse_b:
                     bias = None
             elif (k == 1 and stride == 1 and not transposed_conv and mode == K.MODE_FP32 and winp.dtype == torch.float32
@@ -893,12 +944,13 @@ class Unet(nn.Module):
                 # fp32 mode (round 4): the same queue, the exact-fp32 instantiation of the 1x1 kernel; the bias gradient rides along
                 fuse_b = bias == "colsum"
                 wq.push1x1(winp, dy, gv[pre + "weight"], Ci=ci, Cj=co, hw=(ih, iw), mode=mode, P2=wx2,
-                           dbias=gv[pre + "bias"] if fuse_b else None)
+                           dbias=gv[pre + "bias"] if fuse_b else None, prefill=prefill)
                 if fuse_b:
                     bias = None
             else:
                 if stride == 2:
                     winp = inp                                        # round 1's ring kernel converts while it stages
+                fill()
                 K.conv_wgrad(winp, dy, gv[pre + "weight"], kh=kh, kw=kw, stride=stride, pad=pad, gather_i=True,
                              Ci=ci, Cj=co, grid_g=(ih, iw), grid_d=(oh, ow), mode=mode, P2=wx2,
                              dbias=gv[pre + "bias"] if bias == "colsum" else None)

@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from .lib import ROWSUM_MAX, MiConvDesc, MiGnDesc, MiRowSum, MiWgradDesc, check, load_library
+from .lib import ROWSUM_MAX, WGRAD_STORE, MiConvDesc, MiGnDesc, MiRowSum, MiWgradDesc, check, load_library
 
 MODE_FP32, MODE_BF16 = 0, 1
 
@@ -924,10 +924,13 @@ class WgradQueue:
     layers (1, 2, ...); `flushed` = the largest n such that layers 1..n have ALL been issued (the two kinds flush independently, so a
     count of issued layers would not say that); `on_flush()` is called after every flush.
     Kind 4 (round 4): reductions that leave one partial row per workgroup (channel LayerNorm's dg / db) push (rows, dst) pairs; ONE
-    mi_rowsum_batch launch adds all of them (at the final flush, or right away when a caller flushes kind 4: data parallelism)."""
+    mi_rowsum_batch launch adds all of them (at the final flush, or right away when a caller flushes kind 4: data parallelism).
+    store: the launches WRITE dW (MI_WGRAD_STORE) -- for a gradient buffer whose conv weights were left unfilled; a layer that falls
+    back to conv_wgrad (which can only add) and was pushed with prefill=True has its dW zero-filled first."""
 
-    def __init__(self, group: int = 8, on_flush=None, group_s2=None):
+    def __init__(self, group: int = 8, on_flush=None, group_s2=None, store=False):
         self.group, self.on_flush = max(1, min(8, int(group))), on_flush
+        self.flags = WGRAD_STORE if store else 0
         self.group_s2 = self.group if group_s2 is None else max(1, min(8, int(group_s2)))    # stride-2 layers per launch
         self.items3, self.items1, self.items2, self.items4 = [], [], [], []
         self.pushed = 0
@@ -944,13 +947,15 @@ class WgradQueue:
         return MiWgradDesc(N=P.shape[0], GH=hw[0], GW=hw[1], DH=hw[0], DW=hw[1], Ci=Ci, Cj=Cj, KH=k, KW=k, stride=1, pad=k // 2, gather_i=1,
                            mode=mode, I1=I1, ldp=ld_of(P), ldp2=ld_of(P2) if P2 is not None else 0, ldq=ld_of(Q))
 
-    def push(self, P, Q, dW, *, Ci, Cj, hw, mode, P2=None):
-        """3x3 / stride 1 / pad 1"""
+    def push(self, P, Q, dW, *, Ci, Cj, hw, mode, P2=None, prefill=False):
+        """3x3 / stride 1 / pad 1.  prefill: dW holds no zeros yet (store mode) -- filled here if the layer takes the fallback"""
         d = self._desc(P, Q, 3, Ci, Cj, hw, mode, P2)
         same = (lambda dt: P.dtype == dt and Q.dtype == dt and (P2 is None or P2.dtype == dt))      # noqa: E731
         ok = (USE_WGRAD_TR and self.group > 1 and (same(torch.bfloat16) if mode == MODE_BF16 else same(torch.float32))
               and _query("mi_conv3x3_wgrad_tr_supported", d))      # (mode 0: the exact-fp32 instantiation, fp32 operands)
         if not ok:
+            if prefill:
+                dW.zero_()
             conv_wgrad(P, Q, dW, kh=3, kw=3, stride=1, pad=1, gather_i=True, Ci=Ci, Cj=Cj, grid_g=hw, grid_d=hw, mode=mode, P2=P2)
             return
         self.items3.append((d, P, P2, Q, dW))
@@ -959,8 +964,8 @@ class WgradQueue:
         if len(self.items3) >= self.group:
             self.flush(kinds=(3,))
 
-    def push1x1(self, P, Q, dW, *, Ci, Cj, hw, mode, P2=None, dbias=None):
-        """1x1; dbias (optional) += column sums of Q"""
+    def push1x1(self, P, Q, dW, *, Ci, Cj, hw, mode, P2=None, dbias=None, prefill=False):
+        """1x1; dbias (optional) += column sums of Q; prefill: as in push"""
         d = self._desc(P, Q, 1, Ci, Cj, hw, mode, P2)
         q32 = int(Q.dtype == torch.float32)
         if mode == MODE_FP32:       # exact-fp32 instantiation (round 4): fp32 X and dY
@@ -970,6 +975,8 @@ class WgradQueue:
         ok = (USE_WGRAD_TR and self.group > 1 and dt_ok and (dbias is None or q32)
               and _query("mi_conv1x1_wgrad_tr_supported", d, q32))
         if not ok:
+            if prefill:
+                dW.zero_()
             conv_wgrad(P, Q, dW, kh=1, kw=1, stride=1, pad=0, gather_i=True, Ci=Ci, Cj=Cj, grid_g=hw, grid_d=hw, mode=mode, P2=P2, dbias=dbias)
             return
         self.items1.append((d, P, P2, Q, dW, dbias, q32))
@@ -1030,8 +1037,8 @@ class WgradQueue:
             ws = _workspace(items[0][1].device, need)
 
             def go():
-                check(lib.mi_conv3x3_wgrad_tr_batch(n, descs, arr(items, 1), arr(items, 2), arr(items, 3), arr(items, 4), _p(ws), ws.numel() * 4,
-                                                    _stream()), "mi_conv3x3_wgrad_tr_batch")
+                check(lib.mi_conv3x3_wgrad_tr_batch_ex(n, descs, arr(items, 1), arr(items, 2), arr(items, 3), arr(items, 4), _p(ws), ws.numel() * 4,
+                                                       _stream(), self.flags), "mi_conv3x3_wgrad_tr_batch_ex")
             flops = sum(2.0 * it[0].N * it[0].DH * it[0].DW * it[0].Ci * it[0].Cj * 9 for it in items)
             f32 = items[0][0].mode == MODE_FP32
             nb = sum(it[0].N * it[0].DH * it[0].DW * (it[0].Ci + it[0].Cj) * (4.0 if f32 else 2.0) for it in items)
@@ -1046,8 +1053,8 @@ class WgradQueue:
             ws = _workspace(items[0][1].device, need)
 
             def go1():
-                check(lib.mi_conv1x1_wgrad_tr_batch(n, descs, q32, arr(items, 1), arr(items, 2), arr(items, 3), arr(items, 4), arr(items, 5),
-                                                    _p(ws), ws.numel() * 4, _stream()), "mi_conv1x1_wgrad_tr_batch")
+                check(lib.mi_conv1x1_wgrad_tr_batch_ex(n, descs, q32, arr(items, 1), arr(items, 2), arr(items, 3), arr(items, 4), arr(items, 5),
+                                                       _p(ws), ws.numel() * 4, _stream(), self.flags), "mi_conv1x1_wgrad_tr_batch_ex")
             flops = sum(2.0 * it[0].N * it[0].DH * it[0].DW * it[0].Ci * it[0].Cj for it in items)
             f32 = items[0][0].mode == MODE_FP32
             nb = sum(it[0].N * it[0].DH * it[0].DW * (it[0].Ci * (4.0 if f32 else 2.0) + it[0].Cj * (4.0 if it[6] else 2.0)) for it in items)
@@ -1061,8 +1068,8 @@ class WgradQueue:
             ws = _workspace(items[0][1].device, need)
 
             def go2():
-                check(lib.mi_conv_s2_wgrad_tr_batch(n, descs, arr(items, 1), arr(items, 3), arr(items, 4), _p(ws), ws.numel() * 4, _stream()),
-                      "mi_conv_s2_wgrad_tr_batch")
+                check(lib.mi_conv_s2_wgrad_tr_batch_ex(n, descs, arr(items, 1), arr(items, 3), arr(items, 4), _p(ws), ws.numel() * 4, _stream(),
+                                                       self.flags), "mi_conv_s2_wgrad_tr_batch_ex")
             flops = sum(2.0 * it[0].N * it[0].DH * it[0].DW * it[0].Ci * it[0].Cj * it[0].KH * it[0].KW for it in items)
             nb = sum(it[0].N * it[0].DH * it[0].DW * 2.0 * ((4 if it[0].gather_i else 1) * it[0].Ci + (1 if it[0].gather_i else 4) * it[0].Cj)
                      for it in items)
@@ -1098,6 +1105,14 @@ def _rows_arena(device, nbytes):
         cur = torch.empty((max(int(nbytes) * 2, 16 << 20) + 3) // 4, device=device, dtype=torch.float32)
         _ROWS[device] = cur
     return cur
+
+
+def zero_ranges(table, n, base):
+    """base[off : off + cnt] = 0 for the n (off, cnt) int64 pairs of the device tensor `table`: one kernel launch"""
+    e0 = _probe_open()
+    check(load_library().mi_zero_ranges(_p(table), int(n), _p(base), _stream()), "mi_zero_ranges")
+    if e0 is not None:
+        _probe_close(e0, "zero_ranges_kernel", 0.0, f"{n} ranges", 0.0)
 
 
 def _workspace(device, nbytes):

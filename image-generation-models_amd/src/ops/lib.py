@@ -36,6 +36,9 @@ class MiRowSum(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int), ("cols", C.c_int), ("ld", C.c_int), ("pad_", C.c_int)]
 
 
+WGRAD_STORE = 1       # MI_WGRAD_STORE
+
+
 class MiPcnnConvDesc(C.Structure):
     _fields_ = ([(n, C.c_int) for n in ("N", "H", "W", "Cin", "ldx", "Cout", "ldy", "ntaps")]
                 + [(n, C.c_int * 25) for n in ("tap_dy", "tap_dx", "tap_w")]
@@ -77,6 +80,11 @@ SIGNATURES = {
     "mi_conv_s2_wgrad_f32_supported": [C.POINTER(MiWgradDesc)],
     "mi_conv_s2_wgrad_f32": [C.POINTER(MiWgradDesc), _P, _P, _P, _P, _Z, _P],
     "mi_debug_wgrad_s2_tr_phase": [_I],
+    "mi_conv3x3_wgrad_tr_batch_ex": [_I, C.POINTER(MiWgradDesc), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _Z, _P, C.c_uint],
+    "mi_conv1x1_wgrad_tr_batch_ex": [_I, C.POINTER(MiWgradDesc), C.POINTER(_I), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                     C.POINTER(_P), _P, _Z, _P, C.c_uint],
+    "mi_conv_s2_wgrad_tr_batch_ex": [_I, C.POINTER(MiWgradDesc), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _Z, _P, C.c_uint],
+    "mi_zero_ranges": [_P, _I, _P, _P],
     "mi_debug_spin": [_I, _I, _P, _Z, _I, _P],
     "mi_debug_clock_probe": [_I, _I, _P, _P],
     "mi_pack_weights_tile": [],

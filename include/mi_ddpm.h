@@ -415,6 +415,21 @@ size_t mi_conv_s2_wgrad_tr_batch_workspace(int n, const MiWgradDesc* descs);
 int mi_conv_s2_wgrad_tr_batch(int n, const MiWgradDesc* descs, const void* const* P, const void* const* Q, float* const* dW,
                               void* workspace, size_t ws_bytes, void* stream);
 int mi_debug_wgrad_s2_tr_phase(int phase);
+
+/* The three batched entry points above with a trailing `flags` (flags = 0 is exactly the call above: dW += result).
+ *   MI_WGRAD_STORE   dW = result.  Every element of a layer's dW has one writer per call (the reduce kernel, or the contraction's
+ *                    epilogue when the layer has a single k-slice), so a gradient buffer that is rewritten every step needs neither
+ *                    a zero fill nor the read of those zeros.  Nothing outside [KH][KW][Ci][Cj] is written; the sums and their order
+ *                    are those of the accumulating call.  dbias (1x1) is still an atomic add. */
+#define MI_WGRAD_STORE 1u
+int mi_conv3x3_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, const void* const* P, const void* const* P2,
+                                 const void* const* Q, float* const* dW, void* workspace, size_t ws_bytes, void* stream, unsigned flags);
+int mi_conv1x1_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, const int* q_is_fp32, const void* const* P,
+                                 const void* const* P2, const void* const* Q, float* const* dW, float* const* dbias,
+                                 void* workspace, size_t ws_bytes, void* stream, unsigned flags);
+int mi_conv_s2_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, const void* const* P, const void* const* Q, float* const* dW,
+                                 void* workspace, size_t ws_bytes, void* stream, unsigned flags);
+
 /* Exact-fp32 mode (d->mode = 0), round 6: the same two layers' weight gradients (Conv2d(C, C, 3, 2, 1) of Downsample, ConvTranspose2d(C, C, 4,
  * 2, 1) of Upsample; reference src/models/ddpm.py:70,79 -- aten::convolution_backward (weight)) as k x k gathered problems of the exact-fp32
  * 1x1 weight-gradient kernel (v_mfma_f32_32x32x2_f32 = an fp32 fmaf chain), up to eight taps per launch.  P fp32 [N][..][Ci], Q fp32
@@ -450,6 +465,10 @@ int mi_colsum(int M, int C, const float* x, int ld, float* out, void* stream);
 #define MI_ROWSUM_MAX 16
 typedef struct { const float* src; float* dst; int rows, cols, ld, pad_; } MiRowSum;
 int mi_rowsum_batch(int n, const MiRowSum* items, void* stream);
+/* base[off .. off + cnt) = 0 for the n (off, cnt) pairs (int64, in floats; cnt may be 0) of a table in DEVICE memory, in one kernel
+ * launch (a kernel node under graph capture, never a memset node).  The flat gradient buffer's zero fill without the weight gradients
+ * that MI_WGRAD_STORE writes outright.  The ranges are the caller's: nothing checks them against the buffer. */
+int mi_zero_ranges(const long long* table_dev, int n, float* base, void* stream);
 
 /* ---- GroupNorm(8)+Mish (+time bias, +residual) ---------------------------------------
  * Block's GroupNorm->Mish (ddpm.py:116,62-64), the time-embedding add `h += mlp(t)`
