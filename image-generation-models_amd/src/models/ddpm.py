@@ -57,6 +57,9 @@ class _Entry:
         if self.layout == "convT":           # logical [Cin,Cout,kh,kw], stored [kh,kw,Cin,Cout]
             ci, co, kh, kw = self.shape
             return seg.view(kh, kw, ci, co)
+        if self.layout == "linear":          # logical [out,in] (nn.Linear), stored input-major [in,out] (csrc/latent_disc.hip)
+            o, i = self.shape
+            return seg.view(i, o)
         return seg.view(self.shape)
 
     def logical_view(self, flat: torch.Tensor) -> torch.Tensor:
@@ -65,6 +68,8 @@ class _Entry:
             return sv.permute(3, 2, 0, 1)
         if self.layout == "convT":
             return sv.permute(2, 3, 0, 1)
+        if self.layout == "linear":
+            return sv.t()
         return sv
 
 

@@ -1,11 +1,13 @@
 """MNIST-sized conv encoder / decoder with the reference's surface (src/networks/basic.py:147-204: `ConvEncoder`, `ConvDecoder`,
 what configs/networks/conv_mnist.yaml instantiates) on the HIP kernels.  `norm_type` "batch" (the config default:
 nn.BatchNorm2d with running statistics) and "layer" (nn.GroupNorm(1, C)) are built; same constructors, parameter / buffer names
-(`network.N.weight`, `network.N.running_mean`, ...) and seeded initial weights.  The MLP networks of that file are not on any
-BASELINE config's path.
+(`network.N.weight`, `network.N.running_mean`, ...) and seeded initial weights.
+Of the MLP networks of that file, `MLPEncoder` is built in the one shape the FactorVAE's latent discriminator uses
+(src/models/factor_vae.py:48), on the fused kernels of csrc/latent_disc.hip; `MLPDecoder` is not on any shipped config's path.
 """
 import torch
 
+from ..models.ddpm import _Entry
 from ..ops import functional as K
 from .flatnet import FlatNet
 
@@ -142,3 +144,67 @@ class ConvEncoder(FlatNet, _NormMixin):
                 g = self._norm_bwd(a, st, norm, g, gv)
             g = self._conv_bwd(g, tape[0] if i == 0 else tape[i][2], pre, k, s, p, want_dx=(i > 0 or need_dx))
         return g
+
+
+class MLPEncoder(FlatNet):
+    """The reference's MLPEncoder (src/networks/basic.py:64-112) in the shape the latent discriminators build:
+    Linear(C*w*h, 256) -> GroupNorm(1, 256) -> LeakyReLU(0.2) -> Linear(256, 256) -> BatchNorm1d(256) -> LeakyReLU(0.2) -> Linear(256, 1).
+    Same constructor, parameter / buffer names (`model.0.fc.weight`, `model.1.norm.running_mean`, `classifier.fc.weight`, ...),
+    construction order and seeded default init.  Anything the kernels do not cover raises NotImplementedError.
+    The network is fp32 in every compute mode (`compute_mode="bf16"` too): it is launch-bound, not arithmetic-bound.
+    `disc_forward` / `disc_backward` are what a training step calls (no autograd graph); `forward(x)` gives the logits alone."""
+    KEYS = ("model.0.fc.weight", "model.0.fc.bias", "model.0.norm.weight", "model.0.norm.bias", "model.1.fc.weight", "model.1.fc.bias",
+            "model.1.norm.weight", "model.1.norm.bias", "classifier.fc.weight", "classifier.fc.bias")
+    BF16_SHADOWS = False
+
+    def __init__(self, input_channel, output_channel, hidden_dims, width, height, dropout=0, norm_type="batch", return_features=False,
+                 output_act="identity"):
+        super().__init__()
+        hidden_dims = [int(h) for h in hidden_dims]
+        in_features = int(input_channel) * int(width) * int(height)
+        if (hidden_dims != [K.LATENT_DISC_H] * 2 or int(output_channel) != 1 or dropout != 0 or norm_type != "batch" or return_features
+                or output_act != "identity" or not 1 <= in_features <= 64):
+            raise NotImplementedError("MLPEncoder on the HIP path: hidden_dims=[256, 256], output_channel=1, at most 64 input features, "
+                                      "dropout=0, norm_type='batch', return_features=False, output_act='identity'")
+        self.input_channel, self.output_channel, self.in_features, self.return_features = input_channel, output_channel, in_features, False
+        dims = [in_features] + hidden_dims
+        for i in range(2):
+            self._linear_params(f"model.{i}.fc.", dims[i], dims[i + 1])
+            if i == 0:
+                self._norm_params("model.0.norm.", dims[1])               # first layer: GroupNorm(1, C), no batch norm
+            else:
+                self._batchnorm_params("model.1.norm.", dims[2])
+        self._linear_params("classifier.fc.", dims[2], 1)
+        self._finish()
+
+    def _linear_params(self, pre, i, o):
+        """nn.Linear: weight logical [out, in] stored input-major, torch's seeded default init."""
+        self._entries.append(_Entry(pre + "weight", (o, i), "linear", "kaiming", i, 0))
+        self._entries.append(_Entry(pre + "bias", (o,), "plain", "ubias", i, 0))
+
+    def _tensors(self, views):
+        return [views[k] for k in self.KEYS]
+
+    def disc_forward(self, target, z=None, h=None, eps=None, perm=None):
+        """Logits, least-squares loss against `target` and the tape, from rows z, from (h, eps) or from (h, eps, perm)
+        (K.latent_disc_fwd).  Training mode uses batch statistics and updates the running ones; evaluation mode uses those."""
+        return K.latent_disc_fwd(self._tensors(self._sv), target, z=z, h=h, eps=eps, perm=perm, training=self.training,
+                                 running_mean=self._buffer("model.1.norm.running_mean"), running_var=self._buffer("model.1.norm.running_var"),
+                                 num_batches_tracked=self._buffer("model.1.norm.num_batches_tracked"))
+
+    def disc_backward(self, rec, target, param_grads=True, accumulate=False, scale=1.0, dz=None, dz_scale=1.0, accumulate_dz=False):
+        """Gradients of mean((logit - target)^2) from a `disc_forward` record.  param_grads: into the flat gradient buffer, stored
+        (accumulate=False: every gradient element is written, nothing needs zeroing) or added; dz: see K.latent_disc_bwd."""
+        grads = None
+        if param_grads:
+            self.flat_grads
+            grads = self._tensors(self._gv)
+        return K.latent_disc_bwd(self._tensors(self._sv), rec, target, grads=grads, param_scale=scale, accumulate_params=accumulate, dz=dz,
+                                 dz_scale=dz_scale, accumulate_dz=accumulate_dz)
+
+    def forward(self, x):
+        n = x.shape[0]
+        x = x.reshape(n, -1)
+        if not x.is_cuda:
+            raise RuntimeError("libmi_ddpm kernels need tensors on an MI355X (HIP) device; there is no CPU fallback")
+        return self.disc_forward(0.0, z=x.float().contiguous())["logit"].view(n, 1)

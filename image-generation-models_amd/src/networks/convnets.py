@@ -1,6 +1,7 @@
 """DCGAN-style generator / critic of the reference's conv32 / conv64 networks (src/networks/conv32.py, conv64.py) on the HIP
-kernels, restricted to what the WGAN-GP path uses: `norm_type="layer"` (= nn.GroupNorm(1, C), forced by
-src/models/wgan_gp.py:30-31), Tanh output, no feature extraction.  Same constructors, parameter names (`main.N.weight`) and
+kernels, restricted to what the WGAN-GP and FactorVAE paths use: `norm_type="layer"` (= nn.GroupNorm(1, C), forced by
+src/models/wgan_gp.py:30-31) or `None` (nn.Identity: configs/experiment/factor_vae/*.yaml; the norm slots hold no parameters, so the
+state-dict indices do not move), Tanh output, no feature extraction.  Same constructors, parameter names (`main.N.weight`) and
 seeded initial weights.
 
 Besides forward / backward the critic implements what the gradient penalty needs (wgan_gp.py:83-107):
@@ -20,13 +21,14 @@ class _Decoder(FlatNet):
 
     def __init__(self, input_channel=1, output_channel=3, ngf=32, norm_type="batch", output_act="tanh"):
         super().__init__()
-        if norm_type != "layer" or output_act != "tanh":
-            raise NotImplementedError("only norm_type='layer' + tanh (the WGAN-GP configuration) is built on the HIP path")
-        self.input_channel, self.output_channel = input_channel, output_channel
+        if norm_type not in ("layer", None) or output_act != "tanh":
+            raise NotImplementedError("only norm_type='layer' (WGAN-GP) or None (FactorVAE) + tanh is built on the HIP path")
+        self.input_channel, self.output_channel, self.norm_type = input_channel, output_channel, norm_type
         chans = [input_channel, ngf * 8, ngf * 4, ngf * 2, ngf]
         for i in range(4):
             self._conv_params(f"main.{3 * i}.", chans[i], chans[i + 1], self.K0 if i == 0 else 4, transposed=True)
-            self._norm_params(f"main.{3 * i + 1}.", chans[i + 1])
+            if norm_type is not None:
+                self._norm_params(f"main.{3 * i + 1}.", chans[i + 1])
         self._conv_params("main.12.", ngf, output_channel, 4, transposed=True)
         self._finish()
 
@@ -43,10 +45,13 @@ class _Decoder(FlatNet):
         for i in range(4):
             k, s, p = self._geom(i)
             a = self._conv(h, f"main.{3 * i}.", k, s, p, transposed=True)
-            n, st = K.sample_norm_fwd(a, sv[f"main.{3 * i + 1}.weight"], sv[f"main.{3 * i + 1}.bias"])
+            if self.norm_type is None:
+                n, st = a, None
+            else:
+                n, st = K.sample_norm_fwd(a, sv[f"main.{3 * i + 1}.weight"], sv[f"main.{3 * i + 1}.bias"])
             h = K.relu_fwd(n, inplace=True)
             if record:
-                tape.append((a, st, h))
+                tape.append((a if st is not None else None, st, h))
         out = self._conv(h, "main.12.", 4, 2, 1, transposed=True)
         y = K.tanh_fwd(out._base if out._base is not None else out, inplace=True)          # padded lanes stay 0
         y = y[..., :self.output_channel]
@@ -68,8 +73,9 @@ class _Decoder(FlatNet):
             k, s, p = (4, 2, 1)
             g = self._conv_bwd(g, h, pre, k, s, p, transposed=True)
             K.relu_bwd(h, g, out=g)
-            g = K.sample_norm_bwd(a, st, sv[f"main.{3 * i - 2}.weight"], g, dgamma=gv[f"main.{3 * i - 2}.weight"],
-                                  dbeta=gv[f"main.{3 * i - 2}.bias"], out=g)
+            if st is not None:
+                g = K.sample_norm_bwd(a, st, sv[f"main.{3 * i - 2}.weight"], g, dgamma=gv[f"main.{3 * i - 2}.weight"],
+                                      dbeta=gv[f"main.{3 * i - 2}.bias"], out=g)
         k, s, p = self._geom(0)
         return self._conv_bwd(g, tape[0], "main.0.", k, s, p, transposed=True, want_dx=need_dx)
 
@@ -82,13 +88,13 @@ class _Encoder(FlatNet):
 
     def __init__(self, input_channel, output_channel, ndf, norm_type="batch", return_features=False):
         super().__init__()
-        if norm_type != "layer" or return_features:
-            raise NotImplementedError("only norm_type='layer' without feature extraction (the WGAN-GP configuration) is built on the HIP path")
-        self.input_channel, self.output_channel = input_channel, output_channel
+        if norm_type not in ("layer", None) or return_features:
+            raise NotImplementedError("only norm_type='layer' (WGAN-GP) or None (FactorVAE) without feature extraction is built on the HIP path")
+        self.input_channel, self.output_channel, self.norm_type = input_channel, output_channel, norm_type
         chans = [input_channel, ndf, ndf * 2, ndf * 4, ndf * 8]
         for i in range(4):
             self._conv_params(self.CONVS[i], chans[i], chans[i + 1], 4)
-            if self.NORMS[i]:
+            if self.NORMS[i] and norm_type is not None:
                 self._norm_params(self.NORMS[i], chans[i + 1])
         self._conv_params(self.CONVS[4], ndf * 8, output_channel, self.K0)
         self._finish()
@@ -103,7 +109,7 @@ class _Encoder(FlatNet):
         h = x
         for i in range(4):
             a = self._conv(h, self.CONVS[i], 4, 2, 1)
-            if self.NORMS[i]:
+            if self.NORMS[i] and self.norm_type is not None:
                 n, st = K.sample_norm_fwd(a, sv[self.NORMS[i] + "weight"], sv[self.NORMS[i] + "bias"])
             else:
                 n, st = a, None
@@ -148,6 +154,7 @@ class _Encoder(FlatNet):
     def input_grad_chain(self, tape):
         """d sum(critic(x)) / d x through the input-gradient kernels only (no parameter gradients), every intermediate kept:
         returns (g [N,H,W,4-padded dense], chain) with chain[i] = (d n_i, d a_i) for layer i (d n_0 is None)."""
+        self._need_norms()
         sv = self._sv
         x = tape[0]
         N = x.shape[0]
@@ -173,6 +180,7 @@ class _Encoder(FlatNet):
     def penalty_backward(self, tape, chain, u0):
         """Parameter gradients of a scalar whose gradient wrt the input gradient g is u0 (dense, padded like g); accumulates
         into the flat gradient buffer (call after a backward, or zero the buffer yourself)."""
+        self._need_norms()
         sv = self._sv
         self.flat_grads
         gv = self._gv
@@ -194,6 +202,10 @@ class _Encoder(FlatNet):
         ones[..., 0] = 1.0
         self._wgrad_only(w, ones[..., :self.output_channel], self.CONVS[4], self.K0, 1, 0)
         self.backward_nhwc(tape, None, extra=extra, keep_grads=True)
+
+    def _need_norms(self):
+        if self.norm_type is None:
+            raise NotImplementedError("the gradient-penalty chain is built for norm_type='layer' only (WGAN-GP); norm_type=None has no caller")
 
     def _conv_mode(self):
         from ..models.ddpm import _mode_id

@@ -1579,6 +1579,91 @@ def cvae_latent_bwd(h, eps, labels, dzc, g_kld, dE, g_dev=None):
     return dh
 
 
+# --------------------------------------------------------------------------- latent discriminator (latent_disc.hip)
+LATENT_DISC_H = 256
+
+
+def latent_disc_supported(N, L, H=LATENT_DISC_H) -> bool:
+    return load_library().mi_latent_disc_supported(int(N), int(L), int(H)) == 1
+
+
+def _ld_ptrs(ts):
+    assert len(ts) == 10
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("latent discriminator: parameters / gradients are dense float32 tensors on the HIP device")
+    return (C.c_void_p * 10)(*[t.data_ptr() for t in ts])
+
+
+def _ld_source(z, h, eps, perm):
+    """-> (N, L, the eight source arguments of the C ABI, tensors to keep alive)."""
+    if z is not None:
+        if h is not None or eps is not None or perm is not None:
+            raise RuntimeError("latent discriminator input: either z, or h + eps (+ perm)")
+        _need_gpu(z)
+        if z.dim() != 2 or z.stride(1) != 1 or z.dtype != torch.float32:
+            raise RuntimeError("z: float32 rows with unit column stride")
+        N, L = z.shape
+        return N, L, (_p(z), z.stride(0), _p(None), 0, _p(None), _p(None)), (z,)
+    if h is None or eps is None:
+        raise RuntimeError("latent discriminator input: either z, or h + eps (+ perm)")
+    _need_gpu(h)
+    _need_gpu(eps)
+    N, L = eps.shape
+    if h.dim() != 2 or h.shape[0] != N or h.shape[1] < 2 * L or h.stride(1) != 1 or h.dtype != torch.float32 or eps.dtype != torch.float32:
+        raise RuntimeError("h: float32 rows [mu | log_sigma] of at least 2 L columns, one per row of eps")
+    eps = eps.contiguous()
+    if perm is not None:
+        if not (torch.is_tensor(perm) and perm.is_cuda and perm.dtype == torch.int64 and perm.device == h.device and perm.shape == (L, N)):
+            raise RuntimeError("perm: an int64 tensor [L, N] on the latents' HIP device is expected")
+        perm = perm.contiguous()
+    return N, L, (_p(None), 0, _p(h), h.stride(0), _p(eps), _p(perm)), (h, eps, perm)
+
+
+def latent_disc_fwd(params, target, z=None, h=None, eps=None, perm=None, training=True, running_mean=None, running_var=None,
+                    num_batches_tracked=None, momentum=0.1):
+    """MLPEncoder(L, [256, 256], 1) + least-squares loss in two launches.  params: the ten tensors in the C ABI's order (weights
+    input-major).  Input: z [N, L] rows | h [N, >= 2L] + eps [N, L] (x = mu + exp(log_sigma) eps) | those + perm int64 [L, N]
+    (x[n, j] = z[perm[j, n], j]).  Returns a record: logit [N], loss, mean_logit and mean_sq_logit (device scalars; the last is the loss against target 0) and what `latent_disc_bwd` needs."""
+    N, L, src, keep = _ld_source(z, h, eps, perm)
+    lib = load_library()
+    if lib.mi_latent_disc_supported(N, L, LATENT_DISC_H) != 1:
+        check(-1, "mi_latent_disc_supported")
+    dev = keep[0].device
+    tape = torch.empty(lib.mi_latent_disc_tape_floats(N), device=dev, dtype=torch.float32)
+    out3 = torch.empty(3, device=dev, dtype=torch.float32)
+    if not training and (running_mean is None or running_var is None):
+        raise RuntimeError("evaluation mode needs the running statistics")
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise RuntimeError("num_batches_tracked: int64")
+    check(lib.mi_latent_disc_fwd(N, L, LATENT_DISC_H, *src, _ld_ptrs(params), int(bool(training)), float(target), float(momentum),
+                                 _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(tape), _p(out3), _stream()),
+          "mi_latent_disc_fwd")
+    return {"N": N, "L": L, "src": src, "keep": keep, "training": bool(training), "tape": tape, "out3": out3, "logit": tape[tape.numel() - N:],
+            "loss": out3[0], "mean_logit": out3[1], "mean_sq_logit": out3[2]}
+
+
+def latent_disc_bwd(params, rec, target, grads=None, param_scale=1.0, accumulate_params=False, dz=None, dz_scale=1.0, accumulate_dz=False):
+    """Backward of mean((logit - target)^2) from a forward record (3 launches, 2 without parameter gradients).
+    grads: ten tensors like params, g = (accumulate_params ? g : 0) + param_scale * gradient;  dz: [N, L] rows with unit column
+    stride, dz = (accumulate_dz ? dz : 0) + dz_scale * d loss / d x.  Returns dz."""
+    N, L = rec["N"], rec["L"]
+    lib = load_library()
+    if grads is None and dz is None:
+        raise RuntimeError("latent_disc_bwd: neither parameter gradients nor an input gradient asked for")
+    lddz = 0
+    if dz is not None:
+        _need_gpu(dz)
+        if dz.shape != (N, L) or dz.stride(1) != 1 or dz.dtype != torch.float32:
+            raise RuntimeError("dz: float32 [N, L] rows with unit column stride")
+        lddz = dz.stride(0)
+    ws = torch.empty(lib.mi_latent_disc_workspace_floats(N), device=rec["tape"].device, dtype=torch.float32)
+    check(lib.mi_latent_disc_bwd(N, L, LATENT_DISC_H, *rec["src"], _ld_ptrs(params), int(rec["training"]), float(target), _p(rec["tape"]),
+                                 _p(ws), _ld_ptrs(grads) if grads is not None else None, float(param_scale), int(bool(accumulate_params)),
+                                 _p(dz), lddz, float(dz_scale), int(bool(accumulate_dz)), _stream()), "mi_latent_disc_bwd")
+    return dz
+
+
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)
 def _dense(*ts):
     for t in ts:

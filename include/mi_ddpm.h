@@ -649,6 +649,37 @@ int mi_cvae_latent_fwd(int N, int L, int ncls, const float* h, int ldh, const fl
 int mi_cvae_latent_bwd(int N, int L, int ncls, const float* h, int ldh, const float* eps, const int64_t* labels, const float* dzc,
                        int lddzc, float g_kld, const float* g_dev, float* dh, float* dE, void* stream);
 
+/* ---- latent discriminator (reference src/networks/basic.py:64-112 as src/models/factor_vae.py:48 builds it; csrc/latent_disc.hip) ----
+ * MLPEncoder(L, [256, 256], 1): x [N][L] -> Linear(L,256) -> GroupNorm(1,256) -> LeakyReLU(0.2) -> Linear(256,256) -> BatchNorm1d(256)
+ * -> LeakyReLU(0.2) -> Linear(256,1) = logit[N], with the least-squares loss mean((logit - target)^2).  fp32 in every compute mode; no
+ * atomics, every sum has a fixed order; every element of every output is stored.  2 launches forward, 3 backward (2 without
+ * parameter gradients).
+ * supported: 1 for H == 256, 1 <= L <= 64, 2 <= N <= MI_LATENT_DISC_NMAX, else 0 with a message in mi_last_error().  N == 1 is refused
+ *   because BatchNorm1d has no batch statistics there; NMAX because the forward's tail is ONE workgroup that keeps the N logits in LDS
+ *   (4 B each) and walks the rows serially -- a wider batch wants that tail split, which is not built.
+ * params / grads: host arrays of 10 device pointers: fc1.weight [L][256] (input-major), fc1.bias, norm1.weight, norm1.bias,
+ *   fc2.weight [256 in][256 out], fc2.bias, norm2.weight, norm2.bias, fc3.weight [256], fc3.bias [1].
+ * input, one of: z (rows of ldz >= L; h, eps, perm null) | h = [mu | log_sigma] (rows of ldh >= 2L) + eps [N][L]: x = mu + exp(log_sigma) eps
+ *   formed on the fly | the same + perm int64 [L][N]: x[n][j] = z[perm[j][n]][j] (factor_vae.py:13-22).  A perm entry outside [0, N)
+ *   makes that element 0 and is never used as an address.
+ * fwd: tape (mi_latent_disc_tape_floats(N) floats, 16-byte aligned) = xhat1 [N][256] | h1 [N][256] | a2 [N][256] | LayerNorm (mean, rstd) [N][2]
+ *   | BatchNorm (mean, rstd) [2][256] as fp64 (1024 floats) | logit [N].  Tensors are fp32, sums and BatchNorm's arithmetic fp64;  out3[0] = loss, out3[1] = mean(logit), out3[2] = mean(logit^2) (the loss against target 0).  training != 0: batch statistics, and
+ *   running_mean / running_var (nullable pair; momentum, unbiased variance) and *num_batches_tracked (nullable, += 1) are updated;
+ *   training == 0: the running statistics normalise.
+ * bwd: of the loss against `target` (which may differ from the forward's: the tape does not depend on it), with the forward's input
+ *   and mode.  grads (nullable): g = (accumulate_params ? g : 0) + param_scale * dloss/dparam;  dz (nullable, rows of lddz >= L, not
+ *   with perm): dz = (accumulate_dz ? dz : 0) + dz_scale * dloss/dx.  workspace: mi_latent_disc_workspace_floats(N) floats. */
+#define MI_LATENT_DISC_NMAX 1024
+int mi_latent_disc_supported(int N, int L, int H);
+size_t mi_latent_disc_tape_floats(int N);
+size_t mi_latent_disc_workspace_floats(int N);
+int mi_latent_disc_fwd(int N, int L, int H, const float* z, int ldz, const float* h, int ldh, const float* eps, const int64_t* perm,
+                       const float* const* params, int training, float target, float momentum, float* running_mean, float* running_var,
+                       int64_t* num_batches_tracked, float* tape, float* out3, void* stream);
+int mi_latent_disc_bwd(int N, int L, int H, const float* z, int ldz, const float* h, int ldh, const float* eps, const int64_t* perm,
+                       const float* const* params, int training, float target, const float* tape, float* workspace, float* const* grads,
+                       float param_scale, int accumulate_params, float* dz, int lddz, float dz_scale, int accumulate_dz, void* stream);
+
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
 int mi_time_embed(int B, int dim, const int64_t* t, float* out, void* stream);
