@@ -1,10 +1,13 @@
 """Models with the reference's surface.  Import them from their modules (`src.models.ddpm`, `src.models.factor_vae`, ...), as the
-configs' `_target_`s do; `src.models.FactorVAE` is resolved lazily (the networks import `src.models.ddpm`, so nothing may be imported
-here at package load)."""
+configs' `_target_`s do; `src.models.FactorVAE` and `src.models.AAE` are resolved lazily (the networks import `src.models.ddpm`, so
+nothing may be imported here at package load)."""
 
 
 def __getattr__(name):
     if name == "FactorVAE":
         from .factor_vae import FactorVAE
         return FactorVAE
+    if name == "AAE":
+        from .aae import AAE
+        return AAE
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

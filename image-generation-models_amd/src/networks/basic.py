@@ -19,9 +19,9 @@ class _NormMixin:
         else:
             self._norm_params(pre, c)
 
-    def _norm_fwd(self, a, pre):
+    def _norm_fwd(self, a, pre, bn_updates=1):
         if self.norm_type == "batch":
-            y, mean, rstd = self._bn_fwd(a, pre)
+            y, mean, rstd = self._bn_fwd(a, pre, updates=bn_updates)
             return y, (mean, rstd)
         y, st = K.sample_norm_fwd(a, self._sv[pre + "weight"], self._sv[pre + "bias"])
         return y, st
@@ -118,13 +118,15 @@ class ConvEncoder(FlatNet, _NormMixin):
     def forward(self, x):
         return super().forward(x).reshape(-1, self.output_channel)
 
-    def forward_nhwc(self, x, record=False):
+    def forward_nhwc(self, x, record=False, bn_updates=1):
+        """bn_updates = u: the forward counts as u successive training-mode forwards of this batch for the BatchNorm running
+        statistics and counters (FlatNet._bn_fwd); the default is the single update."""
         tape = [x] if record else None
         h = x
         for pre, k, s, p, norm in self.CONVS:
             a = self._conv(h, pre, k, s, p)
             if norm:
-                n, st = self._norm_fwd(a, norm)
+                n, st = self._norm_fwd(a, norm, bn_updates)
             else:
                 n, st = a, None
             h = K.leaky_relu_fwd(n, 0.2, inplace=True)

@@ -156,14 +156,19 @@ class FlatNet(nn.Module):
             node = node._modules[name]
         return node._buffers[parts[-1]]
 
-    def _bn_fwd(self, x, pre, momentum=0.1, eps=1e-5):
-        """nn.BatchNorm2d forward in the module's current mode; returns (y, mean, rstd)."""
+    def _bn_fwd(self, x, pre, momentum=0.1, eps=1e-5, updates=1):
+        """nn.BatchNorm2d forward in the module's current mode; returns (y, mean, rstd).  updates = u > 1: this forward stands for u
+        successive training-mode forwards of the same batch through the same weights (their outputs are identical): the running
+        statistics end where u momentum updates with the same batch statistics put them -- r (1 - m)^u + s (1 - (1 - m)^u), one update
+        with the momentum 1 - (1 - m)^u -- and num_batches_tracked advances by u."""
         sv = self._sv
         training = self.training
+        if updates != 1:
+            momentum = 1.0 - (1.0 - momentum) ** int(updates)
         y, mean, rstd = K.batchnorm_fwd(x, sv[pre + "weight"], sv[pre + "bias"], self._buffer(pre + "running_mean"),
                                         self._buffer(pre + "running_var"), momentum, eps, training)
         if training:
-            self._buffer(pre + "num_batches_tracked").add_(1)
+            self._buffer(pre + "num_batches_tracked").add_(int(updates))
         return y, mean, rstd
 
     @property

@@ -1664,6 +1664,79 @@ def latent_disc_bwd(params, rec, target, grads=None, param_scale=1.0, accumulate
     return dz
 
 
+# --------------------------------------------------------------------------- row-local latent discriminator (latent_disc_ln.hip)
+LATENT_DISC_LN_LOSSES = {"vanilla": 0, "lsgan": 1}
+
+
+def latent_disc_ln_supported(N0, N1, L, H=LATENT_DISC_H) -> bool:
+    return load_library().mi_latent_disc_ln_supported(int(N0), int(N1), int(L), int(H)) == 1
+
+
+def _ldl_rows(x, what):
+    _need_gpu(x)
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != torch.float32:
+        raise RuntimeError(f"{what}: float32 rows [N, L] with unit column stride")
+    return x
+
+
+def latent_disc_ln_fwd(params, x0, target0, x1=None, target1=0.0, loss_mode="vanilla"):
+    """MLPEncoder(L, [256, 256], 1, norm_type="layer") + the adversarial loss in two launches.  params: the ten tensors in the C ABI's
+    order (weights input-major).  x0 [N0, L] against target0 and (optionally) x1 [N1, L] against target1 go through as ONE pass of
+    N0 + N1 rows; both may be pitched views.  Returns a record: logit [N0 + N1], loss0, loss1, mean_logit0, mean_logit1, d_loss =
+    0.5 (loss0 + loss1) (device scalars) and what `latent_disc_ln_bwd` needs."""
+    x0 = _ldl_rows(x0, "x0")
+    N0, L = x0.shape
+    N1 = 0
+    if x1 is not None:
+        x1 = _ldl_rows(x1, "x1")
+        if x1.shape[1] != L or x1.device != x0.device:
+            raise RuntimeError("x1: rows of the same width and on the same device as x0")
+        N1 = x1.shape[0]
+        if N1 == 0:
+            x1 = None
+    mode = LATENT_DISC_LN_LOSSES.get(loss_mode)
+    if mode is None:
+        raise RuntimeError(f"loss_mode={loss_mode!r}: 'vanilla' or 'lsgan'")
+    lib = load_library()
+    if lib.mi_latent_disc_ln_supported(N0, N1, L, LATENT_DISC_H) != 1:
+        check(-1, "mi_latent_disc_ln_supported")
+    N = N0 + N1
+    tape = torch.empty(lib.mi_latent_disc_ln_tape_floats(N), device=x0.device, dtype=torch.float32)
+    out5 = torch.empty(5, device=x0.device, dtype=torch.float32)
+    src = (N0, N1, L, LATENT_DISC_H, _p(x0), x0.stride(0) if N0 > 1 else max(L, x0.stride(0)), _p(x1),
+           0 if x1 is None else (x1.stride(0) if N1 > 1 else max(L, x1.stride(0))))
+    check(lib.mi_latent_disc_ln_fwd(*src, _ld_ptrs(params), mode, float(target0), float(target1), _p(tape), _p(out5), _stream()),
+          "mi_latent_disc_ln_fwd")
+    return {"N0": N0, "N1": N1, "L": L, "src": src, "keep": (x0, x1), "mode": mode, "tape": tape, "out5": out5,
+            "logit": tape[3 * N * LATENT_DISC_H + 2 * N:3 * N * LATENT_DISC_H + 3 * N], "loss0": out5[0], "loss1": out5[1],
+            "mean_logit0": out5[2], "mean_logit1": out5[3], "d_loss": out5[4]}
+
+
+def latent_disc_ln_bwd(params, rec, target0, target1=0.0, c0=1.0, c1=0.0, grads=None, param_scale=1.0, accumulate_params=False, dx0=None,
+                       dx_scale=1.0, accumulate_dx=False):
+    """Backward of c0 loss0 + c1 loss1 against (target0, target1) from a forward record: 2 launches, 1 without parameter gradients.
+    grads: ten tensors like params, g = (accumulate_params ? g : 0) + param_scale * gradient;  dx0: [N0, L] rows with unit column
+    stride (the first segment's input gradient), dx0 = (accumulate_dx ? dx0 : 0) + dx_scale * gradient.  Returns dx0."""
+    N0, N1, L = rec["N0"], rec["N1"], rec["L"]
+    lib = load_library()
+    if grads is None and dx0 is None:
+        raise RuntimeError("latent_disc_ln_bwd: neither parameter gradients nor an input gradient asked for")
+    lddx = 0
+    if dx0 is not None:
+        _need_gpu(dx0)
+        if dx0.shape != (N0, L) or dx0.stride(1) != 1 or dx0.dtype != torch.float32:
+            raise RuntimeError("dx0: float32 [N0, L] rows with unit column stride")
+        lddx = dx0.stride(0) if N0 > 1 else max(L, dx0.stride(0))
+    ws = None
+    if grads is not None:
+        ws = torch.empty(lib.mi_latent_disc_ln_workspace_floats(N0 + N1), device=rec["tape"].device, dtype=torch.float32)
+    check(lib.mi_latent_disc_ln_bwd(*rec["src"], _ld_ptrs(params), rec["mode"], float(target0), float(target1), float(c0), float(c1),
+                                    _p(rec["tape"]), _p(ws), _ld_ptrs(grads) if grads is not None else None, float(param_scale),
+                                    int(bool(accumulate_params)), _p(dx0), lddx, float(dx_scale), int(bool(accumulate_dx)), _stream()),
+          "mi_latent_disc_ln_bwd")
+    return dx0
+
+
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)
 def _dense(*ts):
     for t in ts:

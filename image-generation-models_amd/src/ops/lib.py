@@ -48,6 +48,7 @@ class MiPcnnConvDesc(C.Structure):
 
 ROWSUM_MAX = 16
 LATENT_DISC_NMAX = 1024   # MI_LATENT_DISC_NMAX
+LATENT_DISC_LN_NMAX = 65536   # MI_LATENT_DISC_LN_NMAX
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
 # name -> argtypes; every function returns int (0 = ok) except the two noted below
@@ -208,6 +209,9 @@ SIGNATURES = {
     "mi_latent_disc_supported": [_I, _I, _I],
     "mi_latent_disc_fwd": [_I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P],
     "mi_latent_disc_bwd": [_I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _F, _P, _P, _P, _F, _I, _P, _I, _F, _I, _P],
+    "mi_latent_disc_ln_supported": [_I, _I, _I, _I],
+    "mi_latent_disc_ln_fwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _F, _F, _P, _P, _P],
+    "mi_latent_disc_ln_bwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _F, _I, _P, _I, _F, _I, _P],
     "mi_adam_tick": [_P, _P],
     "mi_adam_step_dev": [_Z, _P, _P, _P, _P, _P, C.c_double, C.c_double, _F, _F, _P],
     "mi_relu_fwd": [_Z, _P, _P, _P],
@@ -264,6 +268,8 @@ OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_made_dgrad_workspace": ([_I, _I, _I], C.c_size_t),
          "mi_latent_disc_tape_floats": ([_I], C.c_size_t),
          "mi_latent_disc_workspace_floats": ([_I], C.c_size_t),
+         "mi_latent_disc_ln_tape_floats": ([_I], C.c_size_t),
+         "mi_latent_disc_ln_workspace_floats": ([_I], C.c_size_t),
          "mi_chan_layernorm_bwd_part_rows": ([_I, _I], C.c_int),
          "mi_conv_small_wgrad_workspace": ([_I], C.c_size_t)}
 ABI_VERSION = 4

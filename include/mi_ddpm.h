@@ -680,6 +680,37 @@ int mi_latent_disc_bwd(int N, int L, int H, const float* z, int ldz, const float
                        const float* const* params, int training, float target, const float* tape, float* workspace, float* const* grads,
                        float param_scale, int accumulate_params, float* dz, int lddz, float dz_scale, int accumulate_dz, void* stream);
 
+/* ---- row-local latent discriminator (reference src/models/aae.py:42-44: MLPEncoder(L, [256, 256], 1, norm_type="layer");
+ *      csrc/latent_disc_ln.hip) ----
+ * x [N][L] -> Linear(L,256) -> GroupNorm(1,256) -> LeakyReLU(0.2) -> Linear(256,256) -> GroupNorm(1,256) -> LeakyReLU(0.2) -> Linear(256,1)
+ * = logit[N].  No batch statistics: a row's logit depends on that row alone, so N = 1 is legal and the batch may be two SEGMENTS with a
+ * target each -- rows [0, N0) from x0 (rows of ld0 >= L) against target0, rows [N0, N0 + N1) from x1 (rows of ld1 >= L) against target1;
+ * N1 = 0 is allowed (x1 is not read).  The logits of a joint pass equal those of the two separate passes bit for bit.
+ * loss per row, loss_mode 0 (vanilla, binary cross-entropy on the logit): max(x, 0) - x t + log1p(exp(-|x|)), derivative sigmoid(x) - t;
+ *   loss_mode 1 (lsgan): (x - t)^2.
+ * fp32 in every compute mode, sums in fp64 in a fixed order; no atomics; every element of every output is stored.  2 launches forward,
+ * 2 backward, 1 backward when only the input gradient is asked for.
+ * supported: 1 for H == 256, 1 <= L <= 64, N0 >= 1, N1 >= 0, N0 + N1 <= MI_LATENT_DISC_LN_NMAX, else 0 with a message in mi_last_error().
+ *   NMAX: the parameter-gradient sums walk the N0 + N1 rows serially in 34 + ceil(L/8) workgroups; a wider batch wants them split.
+ * params / grads: the ten pointers of mi_latent_disc_fwd in the same order and layout (norm2 is the second GroupNorm's affine pair).
+ * fwd: tape (mi_latent_disc_ln_tape_floats(N0 + N1) floats, 16-byte aligned) = xhat1 [N][256] | h1 [N][256] | xhat2 [N][256] | rstd1 [N]
+ *   | rstd2 [N] | logit [N] | loss per row [N].  out5 = loss0, loss1 (each the mean over its own segment), mean(logit) of segment 0, of
+ *   segment 1, 0.5 (loss0 + loss1); an empty second segment gives loss1 = mean1 = 0.
+ * bwd: of c0 loss0 + c1 loss1 against target0 / target1 (which may differ from the forward's: the tape holds no target-dependent
+ *   value but the per-row loss, which the backward does not read), with the forward's inputs.  grads (nullable; needs workspace,
+ *   mi_latent_disc_ln_workspace_floats(N0 + N1) floats): g = (accumulate_params ? g : 0) + param_scale * d/dparam.  dx0 (nullable; N0 rows
+ *   of lddx >= L, the first segment's input gradient): dx0 = (accumulate_dx ? dx0 : 0) + dx_scale * d/dx0; lanes [L, lddx) are not written. */
+#define MI_LATENT_DISC_LN_NMAX 65536
+int mi_latent_disc_ln_supported(int N0, int N1, int L, int H);
+size_t mi_latent_disc_ln_tape_floats(int N);
+size_t mi_latent_disc_ln_workspace_floats(int N);
+int mi_latent_disc_ln_fwd(int N0, int N1, int L, int H, const float* x0, int ld0, const float* x1, int ld1, const float* const* params,
+                          int loss_mode, float target0, float target1, float* tape, float* out5, void* stream);
+int mi_latent_disc_ln_bwd(int N0, int N1, int L, int H, const float* x0, int ld0, const float* x1, int ld1, const float* const* params,
+                          int loss_mode, float target0, float target1, float c0, float c1, const float* tape, float* workspace,
+                          float* const* grads, float param_scale, int accumulate_params, float* dx0, int lddx, float dx_scale,
+                          int accumulate_dx, void* stream);
+
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
 int mi_time_embed(int B, int dim, const int64_t* t, float* out, void* stream);
