@@ -19,6 +19,7 @@ struct WgradArgs {
     int Mtot, chunk, splits;
     int vec;
     int xcd_map, gx, gy;       // fast kernel: XCD-aware 1-D grid (gx, gy = tiles along Ci, Cj)
+    float* slab;               // generic kernel, slab mode: [splits][taps][Ci][Cj], each k-slice STORES its tile (no atomics); else null
 };
 
 template <int MODE> struct WElem { using type = float; static constexpr int PITCH = 36; };
@@ -178,7 +179,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
         if (more) { store_step(); __syncthreads(); }
     }
 
-    float* out = a.dW + (size_t)tap * a.Ci * a.Cj;
+    // slab mode: slice `split` owns slab [split][tap][Ci][Cj]; the tiles of a (tap, split) cover it, so every element is stored once
+    float* out = a.slab ? a.slab + ((size_t)split * (a.KH * a.KW) + tap) * a.Ci * a.Cj : a.dW + (size_t)tap * a.Ci * a.Cj;
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -189,9 +191,19 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs a) {
             for (int j = 0; j < NJ; ++j) {
                 int col = j0 + wj * WJ + j * 32 + (l & 31);
                 if (col >= a.Cj) continue;
-                atomicAdd(out + (size_t)row * a.Cj + col, acc[i][j][r]);
+                if (a.slab) out[(size_t)row * a.Cj + col] = acc[i][j][r];
+                else atomicAdd(out + (size_t)row * a.Cj + col, acc[i][j][r]);
             }
         }
+}
+
+// dst[e] += slab[0][e] + slab[1][e] + ... in that order (e < n): the fixed-order end of the slab mode
+__global__ __launch_bounds__(256) void slab_sum_kernel(size_t n, int slabs, const float* __restrict__ slab, float* __restrict__ dst) {
+    for (size_t e = blockIdx.x * (size_t)256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
+        float s = 0.f;
+        for (int k = 0; k < slabs; ++k) s += slab[(size_t)k * n + e];
+        dst[e] += s;
+    }
 }
 
 template <int MODE, int BI, int BJ>
@@ -381,7 +393,7 @@ void launch_fast(WgradArgs a, int dw_sh, int dhw_sh, hipStream_t st) {
 
 // out[c] += sum_m x[m*ld + c]
 __global__ __launch_bounds__(256) void colsum_kernel(int M, int C, const float* __restrict__ x, int ld,
-                                                     float* __restrict__ out, int rows_per_block) {
+                                                     float* __restrict__ out, int rows_per_block, float* __restrict__ slab = nullptr) {
     __shared__ float red[256];
     const int cw = min(C, 64);                    // columns handled by this block
     const int c0 = blockIdx.y * 64;
@@ -397,14 +409,47 @@ __global__ __launch_bounds__(256) void colsum_kernel(int M, int C, const float* 
     if (tr == 0 && c < C) {
         float tot = 0.f;
         for (int r = 0; r < nr; ++r) tot += red[r * cw + tc];
-        atomicAdd(out + c, tot);
+        if (slab) slab[(size_t)blockIdx.x * C + c] = tot;           // one partial row per row block, summed in order afterwards
+        else atomicAdd(out + c, tot);
     }
 }
 
 }  // namespace
 
+static int wgrad_plan_splits(const MiWgradDesc* d, int* chunk) {
+    const bool big = d->Ci >= 128 && d->Cj >= 128;
+    const int B = big ? 128 : 64;
+    const int Mtot = d->N * d->DH * d->DW;
+    long base = (long)d->KH * d->KW * ((d->Ci + B - 1) / B) * ((d->Cj + B - 1) / B);
+    long splits = (1024 + base - 1) / base;
+    long maxs = (Mtot + 63) / 64;
+    if (splits > maxs) splits = maxs;
+    if (splits < 1) splits = 1;
+    const int ch = (int)(((Mtot + splits - 1) / splits + 31) / 32 * 32);
+    if (chunk) *chunk = ch;
+    return (Mtot + ch - 1) / ch;
+}
+
+static int conv_wgrad_impl(const MiWgradDesc* d, const float* P, const float* P2, const float* Q, float* dW, float* slab, void* stream);
+
 extern "C" int mi_conv_wgrad(const MiWgradDesc* d, const float* P, const float* P2, const float* Q,
                              float* dW, void* stream) {
+    return conv_wgrad_impl(d, P, P2, Q, dW, nullptr, stream);
+}
+
+extern "C" size_t mi_conv_wgrad_slabs_workspace(const MiWgradDesc* d) {
+    if (!d || d->N <= 0 || d->DH <= 0 || d->DW <= 0 || d->Ci <= 0 || d->Cj <= 0 || d->KH <= 0 || d->KW <= 0) return 0;
+    return (size_t)wgrad_plan_splits(d, nullptr) * d->KH * d->KW * d->Ci * d->Cj * sizeof(float);
+}
+
+extern "C" int mi_conv_wgrad_slabs(const MiWgradDesc* d, const float* P, const float* P2, const float* Q, float* dW, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    MI_REQUIRE(d && ws && (((uintptr_t)ws) & 3) == 0, "needs a workspace");
+    MI_REQUIRE(ws_bytes >= mi_conv_wgrad_slabs_workspace(d) && mi_conv_wgrad_slabs_workspace(d) > 0, "workspace smaller than mi_conv_wgrad_slabs_workspace()");
+    return conv_wgrad_impl(d, P, P2, Q, dW, (float*)ws, stream);
+}
+
+static int conv_wgrad_impl(const MiWgradDesc* d, const float* P, const float* P2, const float* Q, float* dW, float* slab, void* stream) {
     MI_REQUIRE(d && P && Q && dW, "null argument");
     MI_REQUIRE(d->mode == 0 || d->mode == 1, "mode must be 0 or 1");
     MI_REQUIRE(d->I1 == d->Ci || (P2 && d->I1 > 0 && d->I1 < d->Ci && d->I1 % 4 == 0), "bad two-source split");
@@ -414,20 +459,13 @@ extern "C" int mi_conv_wgrad(const MiWgradDesc* d, const float* P, const float* 
     a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.gather_i = d->gather_i;
     a.I1 = d->I1; a.ldp = d->ldp; a.ldp2 = P2 ? d->ldp2 : d->ldp; a.ldq = d->ldq;
     a.Mtot = d->N * d->DH * d->DW;
-    a.xcd_map = 0; a.gx = a.gy = 0;
+    a.xcd_map = 0; a.gx = a.gy = 0; a.slab = slab;
     a.vec = (d->ldp % 4 == 0) && (a.ldp2 % 4 == 0) && (d->ldq % 4 == 0) && (((uintptr_t)P & 15) == 0) &&
             (((uintptr_t)a.P2 & 15) == 0) && (((uintptr_t)Q & 15) == 0);
     const bool big = d->Ci >= 128 && d->Cj >= 128;
-    const int B = big ? 128 : 64;
-    long base = (long)d->KH * d->KW * ((d->Ci + B - 1) / B) * ((d->Cj + B - 1) / B);
-    long splits = (1024 + base - 1) / base;
-    long maxs = (a.Mtot + 63) / 64;
-    if (splits > maxs) splits = maxs;
-    if (splits < 1) splits = 1;
-    a.chunk = (int)(((a.Mtot + splits - 1) / splits + 31) / 32 * 32);
-    a.splits = (a.Mtot + a.chunk - 1) / a.chunk;
+    a.splits = wgrad_plan_splits(d, &a.chunk);
     hipStream_t st = (hipStream_t)stream;
-    {   // aligned bf16 layers on a power-of-two dense grid: the straight-line ring kernel
+    if (!slab) {   // aligned bf16 layers on a power-of-two dense grid: the straight-line ring kernel
         static const int allow_fast = (int)mi_knob("MI_WGRAD_FAST", 1);
         auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
         const int dw_sh = lg(d->DW), dhw_sh = lg(d->DH * d->DW);
@@ -440,6 +478,11 @@ extern "C" int mi_conv_wgrad(const MiWgradDesc* d, const float* P, const float* 
     }
     if (d->mode == 1) { if (big) launch<1, 128, 128>(a, st); else launch<1, 64, 64>(a, st); }
     else              { if (big) launch<0, 128, 128>(a, st); else launch<0, 64, 64>(a, st); }
+    if (slab) {
+        const size_t n = (size_t)d->KH * d->KW * d->Ci * d->Cj;
+        const size_t blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st, n, a.splits, slab, dW);
+    }
     MI_LAUNCH_CHECK();
     return 0;
 }
@@ -447,13 +490,24 @@ extern "C" int mi_conv_wgrad(const MiWgradDesc* d, const float* P, const float* 
 extern "C" int mi_f32_to_bf16_colsum(size_t M, int C, const float* x, int ldx, void* y_bf16, int ldy, float* colsum, void* workspace,
                                      size_t ws_bytes, void* stream);
 
+// out[c] += column sums with the row blocks' partials stored and added in a fixed order: ws = mi_colsum_ordered_workspace(M, C) bytes
+extern "C" size_t mi_colsum_ordered_workspace(int M, int C) { return (M > 0 && C > 0) ? (size_t)((M + 255) / 256) * C * sizeof(float) : 0; }
+extern "C" int mi_colsum_ordered(int M, int C, const float* x, int ld, float* out, void* ws, size_t ws_bytes, void* stream) {
+    MI_REQUIRE(M > 0 && C > 0 && x && out && ld >= C && ws && ws_bytes >= mi_colsum_ordered_workspace(M, C), "bad argument or workspace");
+    const int rows = 256, nb = (M + rows - 1) / rows;
+    hipLaunchKernelGGL(colsum_kernel, dim3(nb, (C + 63) / 64), dim3(256), 0, (hipStream_t)stream, M, C, x, ld, out, rows, (float*)ws);
+    hipLaunchKernelGGL(slab_sum_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, (size_t)C, nb, (const float*)ws, out);
+    MI_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int mi_colsum(int M, int C, const float* x, int ld, float* out, void* stream) {
     MI_REQUIRE(M > 0 && C > 0 && x && out, "bad argument");
     if (C % 4 == 0 && C >= 4 && C <= 1024 && ld % 4 == 0 && (((uintptr_t)x) & 15) == 0)       // float4 rows, several loads in flight
         return mi_f32_to_bf16_colsum((size_t)M, C, x, ld, nullptr, 0, out, nullptr, 0, stream);
     int rows = 256;
     dim3 grid((M + rows - 1) / rows, (C + 63) / 64);
-    hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, M, C, x, ld, out, rows);
+    hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, (hipStream_t)stream, M, C, x, ld, out, rows, (float*)nullptr);
     MI_LAUNCH_CHECK();
     return 0;
 }

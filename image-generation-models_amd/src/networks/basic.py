@@ -13,6 +13,33 @@ from .flatnet import FlatNet
 
 
 class _NormMixin:
+    # Opt-in (the GAN sets it on its two nets): BatchNorm and the activation behind it run as one segmented pass (K.bn_seg_fwd / K.bn_seg_bwd,
+    # csrc/bn_seg.hip) -- 2 launches each way where the default path takes 4, and statistics per segment of the batch.  The default
+    # path, which the VAE, cVAE and AAE run, launches what it always launched.
+    fused_norm_act = False
+
+    def use_fused_norm_act(self, on=True):
+        if on and self.norm_type != "batch":
+            raise NotImplementedError("fused_norm_act: the segmented kernels are BatchNorm's (norm_type='batch')")
+        self.fused_norm_act = bool(on)
+        return self
+
+    def _check_segments(self, segments, bn_updates=1):
+        if segments != 1 and not self.fused_norm_act:
+            raise RuntimeError("segments > 1 needs the segmented BatchNorm path: use_fused_norm_act()")
+        if self.fused_norm_act and bn_updates != 1:
+            raise RuntimeError("bn_updates is the default path's; the segmented path counts one update per segment")
+
+    def _norm_act_fwd(self, a, pre, act, slope, segments):
+        """-> (h, st): the activated output and the tape's statistics entry, ("seg", mean[S, C], rstd[S, C])."""
+        h, mean, rstd = self._bn_seg_fwd(a, pre, act, slope, segments)
+        return h, ("seg", mean, rstd)
+
+    def _norm_act_bwd(self, a, st, h, pre, act, slope, g, gv):
+        """Through the activation and the norm in one pass, in place in g; gv = {}: no parameter gradients."""
+        return K.bn_seg_bwd(a, st[1], st[2], self._sv[pre + "weight"], h, g, act=act, slope=slope, dgamma=gv.get(pre + "weight"),
+                            dbeta=gv.get(pre + "bias"), accumulate=True, out=g)
+
     def _declare_norm(self, pre, c):
         if self.norm_type == "batch":
             self._batchnorm_params(pre, c)
@@ -30,6 +57,10 @@ class _NormMixin:
         if self.norm_type == "batch":
             return K.batchnorm_bwd(a, st[0], st[1], self._sv[pre + "weight"], g, dgamma=gv[pre + "weight"], dbeta=gv[pre + "bias"], out=g)
         return K.sample_norm_bwd(a, st, self._sv[pre + "weight"], g, dgamma=gv[pre + "weight"], dbeta=gv[pre + "bias"], out=g)
+
+
+def _is_seg(st):
+    return isinstance(st, tuple) and len(st) == 3 and isinstance(st[0], str)
 
 
 def _check_norm(norm_type):
@@ -58,14 +89,19 @@ class ConvDecoder(FlatNet, _NormMixin):
     def forward(self, x):
         return super().forward(x.reshape(x.shape[0], -1, 1, 1))
 
-    def forward_nhwc(self, z, record=False):
+    def forward_nhwc(self, z, record=False, segments=1):
+        """segments = S (the segmented path only): the batch is S equal batches, each with its own BatchNorm statistics."""
+        self._check_segments(segments)
         tape = [z] if record else None
         h = z
         for i in range(3):
             k, s, p = self.GEOM[i]
             a = self._conv(h, f"network.{3 * i}.", k, s, p, transposed=True)
-            n, st = self._norm_fwd(a, f"network.{3 * i + 1}.")
-            h = K.relu_fwd(n, inplace=True)
+            if self.fused_norm_act:
+                h, st = self._norm_act_fwd(a, f"network.{3 * i + 1}.", "relu", 0.0, segments)
+            else:
+                n, st = self._norm_fwd(a, f"network.{3 * i + 1}.")
+                h = K.relu_fwd(n, inplace=True)
             if record:
                 tape.append((a, st, h))
         k, s, p = self.GEOM[3]
@@ -90,6 +126,9 @@ class ConvDecoder(FlatNet, _NormMixin):
             a, st, h = tape[i]
             k, s, p = self.GEOM[i]
             g = self._conv_bwd(g, h, f"network.{3 * i}.", k, s, p, transposed=True)
+            if _is_seg(st):
+                g = self._norm_act_bwd(a, st, h, f"network.{3 * i - 2}.", "relu", 0.0, g, gv)
+                continue
             K.relu_bwd(h, g, out=g)
             g = self._norm_bwd(a, st, f"network.{3 * i - 2}.", g, gv)
         k, s, p = self.GEOM[0]
@@ -118,13 +157,21 @@ class ConvEncoder(FlatNet, _NormMixin):
     def forward(self, x):
         return super().forward(x).reshape(-1, self.output_channel)
 
-    def forward_nhwc(self, x, record=False, bn_updates=1):
+    def forward_nhwc(self, x, record=False, bn_updates=1, segments=1):
         """bn_updates = u: the forward counts as u successive training-mode forwards of this batch for the BatchNorm running
-        statistics and counters (FlatNet._bn_fwd); the default is the single update."""
+        statistics and counters (FlatNet._bn_fwd); the default is the single update.
+        segments = S (the segmented path only, `use_fused_norm_act`): x holds S equal batches one after the other; every BatchNorm
+        layer keeps statistics per batch and updates its running statistics S times, first batch first -- what S forwards do."""
+        self._check_segments(segments, bn_updates)
         tape = [x] if record else None
         h = x
         for pre, k, s, p, norm in self.CONVS:
             a = self._conv(h, pre, k, s, p)
+            if norm and self.fused_norm_act:
+                h, st = self._norm_act_fwd(a, norm, "leaky_relu", 0.2, segments)
+                if record:
+                    tape.append((a, st, h))
+                continue
             if norm:
                 n, st = self._norm_fwd(a, norm, bn_updates)
             else:
@@ -135,16 +182,23 @@ class ConvEncoder(FlatNet, _NormMixin):
         out = self._conv(h, "network.8.", 4, 1, 0)
         return out, tape
 
-    def backward_nhwc(self, tape, dout, need_dx=False):
-        gv = self._begin_backward()
-        g = self._conv_bwd(dout, tape[3][2], "network.8.", 4, 1, 0)
+    def backward_nhwc(self, tape, dout, need_dx=False, param_grads=True):
+        """param_grads=False: the input gradient only -- no weight, bias or affine gradient is computed and the gradient buffer is
+        left alone (a GAN's generator phase needs nothing else from its discriminator)."""
+        gv = self._begin_backward() if param_grads else {}
+        g = self._conv_bwd(dout, tape[3][2], "network.8.", 4, 1, 0, want_dw=param_grads)
         for i in range(2, -1, -1):
             pre, k, s, p, norm = self.CONVS[i]
             a, st, h = tape[i + 1]
-            K.leaky_relu_bwd(h, g, 0.2, out=g)
-            if st is not None:
-                g = self._norm_bwd(a, st, norm, g, gv)
-            g = self._conv_bwd(g, tape[0] if i == 0 else tape[i][2], pre, k, s, p, want_dx=(i > 0 or need_dx))
+            if _is_seg(st):
+                g = self._norm_act_bwd(a, st, h, norm, "leaky_relu", 0.2, g, gv)
+            else:
+                K.leaky_relu_bwd(h, g, 0.2, out=g)
+                if st is not None:
+                    if not param_grads:
+                        raise RuntimeError("param_grads=False is built on the segmented BatchNorm path: use_fused_norm_act()")
+                    g = self._norm_bwd(a, st, norm, g, gv)
+            g = self._conv_bwd(g, tape[0] if i == 0 else tape[i][2], pre, k, s, p, want_dx=(i > 0 or need_dx), want_dw=param_grads)
         return g
 
 

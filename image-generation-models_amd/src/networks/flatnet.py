@@ -44,6 +44,12 @@ class FlatNet(nn.Module):
     # that need them.  Off for nets whose shapes those kernels do not cover (28x28 MNIST: odd extents) -- there the extra launch
     # only costs (measured: 100.8k -> 90.3k images/s for the VAE).
     BF16_SHADOWS = True
+    # reproducible = True (an instance's choice; the GAN's nets): no kernel of the net combines partial sums with atomics, so its
+    # outputs and gradients depend on the operands alone and two runs give the same bits.  The whole-input convolution (a GEMM with few
+    # rows) keeps the one-workgroup-per-tile GEMM, where the default splits its long contraction over workgroups that add with fp32
+    # atomics; weight and bias gradients go through the slab mode of the generic weight-gradient kernel and the ordered column sum
+    # (K.conv_wgrad / K.colsum with ordered=True), whose partial sums are stored and added in a fixed order.
+    reproducible = False
 
     def __init__(self):
         super().__init__()
@@ -171,6 +177,18 @@ class FlatNet(nn.Module):
             self._buffer(pre + "num_batches_tracked").add_(int(updates))
         return y, mean, rstd
 
+    def _bn_seg_fwd(self, x, pre, act=None, slope=0.2, segments=1, momentum=0.1, eps=1e-5):
+        """nn.BatchNorm2d + activation over `segments` equal batches in the module's current mode (K.bn_seg_fwd): returns
+        (y, mean[S, C], rstd[S, C]).  Training mode updates the running statistics once per segment, in order, and advances
+        num_batches_tracked by the segment count -- what that many separate forwards do."""
+        sv = self._sv
+        training = self.training
+        y, mean, rstd = K.bn_seg_fwd(x, sv[pre + "weight"], sv[pre + "bias"], segments, self._buffer(pre + "running_mean"),
+                                     self._buffer(pre + "running_var"), momentum, eps, training, act, slope)
+        if training:
+            self._buffer(pre + "num_batches_tracked").add_(int(segments))
+        return y, mean, rstd
+
     @property
     def flat_params(self) -> torch.Tensor:
         return self._flat
@@ -262,7 +280,7 @@ class FlatNet(nn.Module):
             a = inp.view(n, kh * kw * ci)
             b = w.view(1, kh * kw * ci) if co == 1 else w.view(kh * kw * ci, co)
             y = K.small_gemm(False, co == 1, a, b, bias=self._sv[pre + "bias"] if bias else None, out=out.view(n, -1)[:, :co],
-                             accumulate=True, allow_split=True)
+                             accumulate=True, allow_split=not self.reproducible)
             if y is not None:
                 return out[..., :co]
         b = self._sv[pre + "bias"] if bias else None
@@ -290,12 +308,12 @@ class FlatNet(nn.Module):
             pass
         elif transposed:       # dW[tap][ci][co] = sum over input pixels x[j] * dy[scatter(j, tap)]
             K.conv_wgrad(inp, dy, gv[pre + "weight"], kh=kh, kw=kw, stride=stride, pad=pad, gather_i=False, Ci=ci, Cj=co,
-                         grid_g=(oh, ow), grid_d=(ih, iw), mode=mode)
+                         grid_g=(oh, ow), grid_d=(ih, iw), mode=mode, ordered=self.reproducible)
             if bias:
-                K.colsum(dy, gv[pre + "bias"])
+                K.colsum(dy, gv[pre + "bias"], ordered=self.reproducible)
         else:
             K.conv_wgrad(inp, dy, gv[pre + "weight"], kh=kh, kw=kw, stride=stride, pad=pad, gather_i=True, Ci=ci, Cj=co,
-                         grid_g=(ih, iw), grid_d=(oh, ow), mode=mode, dbias=gv[pre + "bias"] if bias else None)
+                         grid_g=(ih, iw), grid_d=(oh, ow), mode=mode, dbias=gv[pre + "bias"] if bias else None, ordered=self.reproducible)
         if not want_dx:
             return None
         wb = None

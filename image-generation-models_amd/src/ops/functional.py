@@ -806,9 +806,11 @@ def conv1x1_small_cout(op, a, w, *, b=None, bias=None, out=None, Cs=None, accumu
     return out
 
 
-def conv_wgrad(P, Q, dW, *, kh, kw, stride, pad, gather_i, Ci, Cj, grid_g, grid_d, mode, P2=None, dbias=None):
+def conv_wgrad(P, Q, dW, *, kh, kw, stride, pad, gather_i, Ci, Cj, grid_g, grid_d, mode, P2=None, dbias=None, ordered=False):
     """dW[tap][i][j] += sum P*Q (see MiWgradDesc).  dW: flat fp32 buffer of kh*kw*Ci*Cj.
-    dbias (optional): dbias[j] += sum over pixels of Q -- fused when the fast kernel runs, else a colsum pass."""
+    dbias (optional): dbias[j] += sum over pixels of Q -- fused when the fast kernel runs, else a colsum pass.
+    ordered: the generic kernel in slab mode (mi_conv_wgrad_slabs) and the ordered column sum -- partial sums are stored and added
+    in a fixed order, no atomics: two runs give the same bits (fp32 operands)."""
     _need_gpu(P)
     N = P.shape[0]
     I1 = P.shape[3] if P2 is not None else Ci
@@ -816,6 +818,14 @@ def conv_wgrad(P, Q, dW, *, kh, kw, stride, pad, gather_i, Ci, Cj, grid_g, grid_
                     stride=stride, pad=pad, gather_i=int(gather_i), mode=mode, I1=I1, ldp=ld_of(P),
                     ldp2=ld_of(P2) if P2 is not None else 0, ldq=ld_of(Q))
     lib = load_library()
+    if ordered:
+        if _b16(P) or _b16(Q):
+            raise RuntimeError("conv_wgrad(ordered=True) takes fp32 operands")
+        ws = _workspace(P.device, lib.mi_conv_wgrad_slabs_workspace(C.byref(d)))
+        check(lib.mi_conv_wgrad_slabs(C.byref(d), _p(P), _p(P2), _p(Q), _p(dW), _p(ws), ws.numel() * 4, _stream()), "mi_conv_wgrad_slabs")
+        if dbias is not None:
+            colsum(Q, dbias, ordered=True)
+        return
     fast = bool(lib.mi_conv3x3_wgrad_supported(C.byref(d)))
     use_tr = bool(USE_WGRAD_TR and dbias is None and kh == 3 and _b16(P) and _b16(Q) and (P2 is None or _b16(P2))
                   and _query("mi_conv3x3_wgrad_tr_supported", d))
@@ -1131,10 +1141,19 @@ def _rows(x):
     return x.shape[0] * x.shape[1] * x.shape[2] if x.dim() == 4 else x.shape[0]
 
 
-def colsum(x, out, defer=None):
-    """out[c] += sum over pixels of x[..., c]; defer (a WgradQueue): as partial rows, added by the queue's batched row sum"""
+def colsum(x, out, defer=None, ordered=False):
+    """out[c] += sum over pixels of x[..., c]; defer (a WgradQueue): as partial rows, added by the queue's batched row sum;
+    ordered: partial rows stored and added in a fixed order (mi_colsum_ordered: no atomics, two runs give the same bits)"""
     Cc = x.shape[-1]
     M = _rows(x)
+    if ordered:
+        _need_gpu(x)
+        if x.dtype != torch.float32:
+            raise RuntimeError("colsum(ordered=True) takes an fp32 tensor")
+        lib = load_library()
+        ws = _workspace(x.device, lib.mi_colsum_ordered_workspace(M, Cc))
+        check(lib.mi_colsum_ordered(M, Cc, _p(x), ld_of(x), _p(out), _p(ws), ws.numel() * 4, _stream()), "mi_colsum_ordered")
+        return
     if defer is not None and Cc % 4 == 0 and 4 <= Cc <= 1024 and _colsum_deferred(x, None, out, defer):
         return
     e0 = _probe_open()
@@ -1735,6 +1754,88 @@ def latent_disc_ln_bwd(params, rec, target0, target1=0.0, c0=1.0, c1=0.0, grads=
                                     int(bool(accumulate_params)), _p(dx0), lddx, float(dx_scale), int(bool(accumulate_dx)), _stream()),
           "mi_latent_disc_ln_bwd")
     return dx0
+
+
+# --------------------------------------------------------------------------- plain GAN operators (bn_seg.hip)
+BN_SEG_ACTS = {None: 0, "none": 0, "relu": 1, "leaky_relu": 2}
+ADV_LOSSES = {"vanilla": 0, "lsgan": 1, "hinge": 2}
+_BN_SEG_WS = {}
+
+
+def _bn_seg_ws(device, S, M, Cc):
+    """The partial-sums workspace: any content will do (every slot a call reads, it wrote), so one buffer per device is reused."""
+    need = load_library().mi_bn_seg_workspace(S, M, Cc)
+    if need == 0:
+        raise RuntimeError(f"bn_seg: S={S}, M={M}, C={Cc} is not covered (C % 4 == 0, C/4 a power of two <= 256)")
+    ws = _BN_SEG_WS.get(device)
+    if ws is None or ws.numel() * 8 < need:
+        ws = torch.empty(max(need // 8, 1 << 16), device=device, dtype=torch.float64)
+        _BN_SEG_WS[device] = ws
+    return ws
+
+
+def _bn_seg_shape(x, segments):
+    Cc = x.shape[-1]
+    rows = x.numel() // Cc
+    S = int(segments)
+    if S < 1 or rows % S != 0 or x.shape[0] % S != 0:
+        raise RuntimeError(f"segments={segments}: the {x.shape[0]} samples do not split into that many equal segments")
+    return S, rows // S, Cc
+
+
+def bn_seg_fwd(x, gamma, beta, segments=1, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, training=True, act=None, slope=0.2):
+    """nn.BatchNorm2d + activation on a dense NHWC tensor whose leading dimension holds `segments` equal batches, each with its own
+    batch statistics and its own running-statistics update (segment 0 first) -> (y, mean[S, C], rstd[S, C]).  Two launches; one in
+    evaluation mode, where every segment uses the running statistics.  act: None, "relu" or "leaky_relu" (slope)."""
+    _need_gpu(x); _dense(x)
+    S, M, Cc = _bn_seg_shape(x, segments)
+    y = torch.empty_like(x)
+    mean = torch.empty((S, Cc), device=x.device, dtype=torch.float32)
+    rstd = torch.empty((S, Cc), device=x.device, dtype=torch.float32)
+    ws = _bn_seg_ws(x.device, S, M, Cc) if training else None
+    check(load_library().mi_bn_seg_fwd(S, M, Cc, _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+                                       momentum, eps, int(bool(training)), BN_SEG_ACTS[act], slope, _p(ws), _stream()), "mi_bn_seg_fwd")
+    return y, mean, rstd
+
+
+def bn_seg_bwd(x, mean, rstd, gamma, y, dy, act=None, slope=0.2, dgamma=None, dbeta=None, accumulate=False, out=None):
+    """Backward of `bn_seg_fwd` in training mode from its input x, its saved statistics and its activated output y; the segment count
+    is mean's leading dimension.  dx (out=dy works in place); dgamma / dbeta (optional) are stored, or added to with accumulate."""
+    _need_gpu(x); _dense(x, y, dy, out)
+    S, M, Cc = _bn_seg_shape(x, mean.shape[0])
+    dx = torch.empty_like(x) if out is None else out
+    check(load_library().mi_bn_seg_bwd(S, M, Cc, _p(x), _p(mean), _p(rstd), _p(gamma), _p(y), _p(dy), _p(dx), _p(dgamma), _p(dbeta),
+                                       int(bool(accumulate)), BN_SEG_ACTS[act], slope, _p(_bn_seg_ws(x.device, S, M, Cc)), _stream()),
+          "mi_bn_seg_bwd")
+    return dx
+
+
+def adv_loss(logit, targets, loss_mode="vanilla", scale=1.0, want_grad=True):
+    """The reference's adversarial_loss (src/utils/losses.py:4-24) per segment of the logits: targets = one bool per segment (True:
+    "real").  logit: [N] or a discriminator's NHWC output [N, 1, 1, 1] (a view of a padded buffer: its pitch goes to the kernel).
+    Returns (loss[S], mean_logit[S], dlogit) with dlogit = scale * d loss_s / d logit, shaped like logit -- for an NHWC logit a view
+    of a zero-padded [N, 1, 1, 4] buffer, what the convolutions' backward reads -- or None.  "hinge" is the reference's formula:
+    max(1 - x, 1) for real targets."""
+    _need_gpu(logit)
+    N = logit.shape[0]
+    if logit.numel() != N or logit.dtype != torch.float32 or N < 1:
+        raise RuntimeError("adv_loss: float32 logits [N] or [N, 1, 1, 1] are expected")
+    mode = ADV_LOSSES.get(loss_mode)
+    if mode is None:
+        raise NotImplementedError(f"loss_mode={loss_mode!r}: 'vanilla', 'lsgan' or 'hinge'")
+    targets = [int(bool(t)) for t in targets]
+    S = len(targets)
+    if S < 1 or N % S != 0:
+        raise RuntimeError(f"adv_loss: {N} logits do not split into {S} equal segments")
+    out = torch.empty((2, S), device=logit.device, dtype=torch.float32)
+    dlogit, lddl = None, 0
+    if want_grad and logit.dim() == 4:
+        dlogit, lddl = torch.zeros((N, 1, 1, 4), device=logit.device, dtype=torch.float32)[..., :1], 4
+    elif want_grad:
+        dlogit, lddl = torch.empty(N, device=logit.device, dtype=torch.float32), 1
+    check(load_library().mi_adv_loss(S, N // S, mode, (C.c_int * S)(*targets), float(scale), _p(logit), max(1, logit.stride(0)), _p(out[0]),
+                                     _p(out[1]), _p(dlogit), lddl, _stream()), "mi_adv_loss")
+    return out[0], out[1], dlogit
 
 
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)

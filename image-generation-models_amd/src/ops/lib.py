@@ -166,6 +166,8 @@ SIGNATURES = {
     "mi_conv3x3_wgrad_ws": [C.POINTER(MiWgradDesc), _P, _P, _P, _P, _P, _Z, _P],
     "mi_conv3x3_wgrad_bias": [C.POINTER(MiWgradDesc), _P, _P, _P, _P, _P, _P, _Z, _P],
     "mi_colsum": [_I, _I, _P, _I, _P, _P],
+    "mi_colsum_ordered": [_I, _I, _P, _I, _P, _P, _Z, _P],
+    "mi_conv_wgrad_slabs": [C.POINTER(MiWgradDesc), _P, _P, _P, _P, _P, _Z, _P],
     "mi_gn_mish_fwd": [C.POINTER(MiGnDesc), _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "mi_gn_mish_bwd": [C.POINTER(MiGnDesc), _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P],
     "mi_chan_layernorm_fwd": [_I, _I, _P, _I, _P, _P, _F, _P, _I, _P],
@@ -212,6 +214,10 @@ SIGNATURES = {
     "mi_latent_disc_ln_supported": [_I, _I, _I, _I],
     "mi_latent_disc_ln_fwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _F, _F, _P, _P, _P],
     "mi_latent_disc_ln_bwd": [_I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _F, _F, _F, _F, _P, _P, _P, _F, _I, _P, _I, _F, _I, _P],
+    "mi_bn_seg_rows_per_workgroup": [_I, _I],
+    "mi_bn_seg_fwd": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _F, _P, _P],
+    "mi_bn_seg_bwd": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
+    "mi_adv_loss": [_I, _I, _I, C.POINTER(C.c_int), _F, _P, _I, _P, _P, _P, _I, _P],
     "mi_adam_tick": [_P, _P],
     "mi_adam_step_dev": [_Z, _P, _P, _P, _P, _P, C.c_double, C.c_double, _F, _F, _P],
     "mi_relu_fwd": [_Z, _P, _P, _P],
@@ -270,6 +276,9 @@ OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_latent_disc_workspace_floats": ([_I], C.c_size_t),
          "mi_latent_disc_ln_tape_floats": ([_I], C.c_size_t),
          "mi_latent_disc_ln_workspace_floats": ([_I], C.c_size_t),
+         "mi_bn_seg_workspace": ([_I, _I, _I], C.c_size_t),
+         "mi_colsum_ordered_workspace": ([_I, _I], C.c_size_t),
+         "mi_conv_wgrad_slabs_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),
          "mi_chan_layernorm_bwd_part_rows": ([_I, _I], C.c_int),
          "mi_conv_small_wgrad_workspace": ([_I], C.c_size_t)}
 ABI_VERSION = 4

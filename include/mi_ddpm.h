@@ -459,6 +459,16 @@ int mi_f32_to_bf16_colsum_part(size_t M, int C, const float* x, int ldx, void* y
                                int* rows, void* stream);
 /* out[c] += sum_m x[m*ld + c]  (bias gradients) */
 int mi_colsum(int M, int C, const float* x, int ld, float* out, void* stream);
+/* The same sums with no atomics: every row block stores a partial row into ws (mi_colsum_ordered_workspace(M, C) bytes, any content),
+ * a second launch adds them in order.  Two runs give the same bits. */
+size_t mi_colsum_ordered_workspace(int M, int C);
+int mi_colsum_ordered(int M, int C, const float* x, int ld, float* out, void* ws, size_t ws_bytes, void* stream);
+/* mi_conv_wgrad's generic kernel with no atomics: each slice of the pixel axis STORES its tiles into its own slab of ws
+ * ([slices][KH*KW][Ci][Cj] floats, mi_conv_wgrad_slabs_workspace(d) bytes, any content) and a second launch adds the slabs onto dW in
+ * slice order.  Same descriptors, same slicing; two runs give the same bits. */
+size_t mi_conv_wgrad_slabs_workspace(const MiWgradDesc* d);
+int mi_conv_wgrad_slabs(const MiWgradDesc* d, const float* P, const float* P2, const float* Q, float* dW, void* ws, size_t ws_bytes,
+                        void* stream);
 /* dst[c] += sum_{r < rows} src[r*ld + c], c < cols, for up to MI_ROWSUM_MAX items in ONE launch: the second pass of the reductions
  * that leave one partial row per workgroup (mi_chan_layernorm_bwd_part) -- device-scope atomics on one address serialise, so 512
  * workgroups adding to the same C addresses cost ~10 us at the end of every launch; here an address receives rows / 64 atomics. */
@@ -710,6 +720,34 @@ int mi_latent_disc_ln_bwd(int N0, int N1, int L, int H, const float* x0, int ld0
                           int loss_mode, float target0, float target1, float c0, float c1, const float* tape, float* workspace,
                           float* const* grads, float param_scale, int accumulate_params, float* dx0, int lddx, float dx_scale,
                           int accumulate_dx, void* stream);
+
+/* ---- plain GAN (reference src/models/gan.py, src/utils/losses.py:4-24): segmented BatchNorm + activation, adversarial losses ----
+ * x: dense NHWC rows [S*M][C] fp32, S >= 1 segments of M rows each; C as mi_batchnorm_fwd (C % 4 == 0, C/4 a power of two <= 256).
+ * act: 0 none, 1 ReLU, 2 LeakyReLU(slope).  Two launches each way: per-workgroup fp64 partial sums STORED into a workspace slot per
+ * (segment, workgroup), then an apply pass whose workgroups add their channels' partials in a fixed order and stream the tensor.  No
+ * atomics, no zero-on-entry workspace, no grid sync: two runs give the same bits.  ws: mi_bn_seg_workspace(S, M, C) bytes, 8-byte
+ * aligned, any content.  mi_bn_seg_rows_per_workgroup(M, C): the rows one sums workgroup walks (a function of M and C alone).
+ * fwd, training != 0: y = act(gamma (x - mean_s) rstd_s + beta) with the mean and biased variance of segment s; mean / rstd [S][C] are
+ *   left for the backward; running statistics (nullable) take the S updates in segment order, s = 0 first (torch's momentum rule,
+ *   unbiased variance, M == 1: the biased one), one thread per channel.  training == 0: every segment uses the running statistics.
+ *   y must not alias x.
+ * bwd (of the training-mode forward): g = act'(y) dy from the activated OUTPUT y (the convention of mi_leaky_relu_bwd), never written;
+ *   dx = gamma rstd_s (g - S0_s / M - xhat S1_s / M), dx may alias dy; dgamma = sum_s S1_s, dbeta = sum_s S0_s (nullable), stored
+ *   (accumulate == 0) or added (accumulate != 0). */
+size_t mi_bn_seg_workspace(int S, int M, int C);
+int mi_bn_seg_rows_per_workgroup(int M, int C);
+int mi_bn_seg_fwd(int S, int M, int C, const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                  float* running_mean, float* running_var, float momentum, float eps, int training, int act, float slope, void* ws,
+                  void* stream);
+int mi_bn_seg_bwd(int S, int M, int C, const float* x, const float* mean, const float* rstd, const float* gamma, const float* y,
+                  const float* dy, float* dx, float* dgamma, float* dbeta, int accumulate, int act, float slope, void* ws, void* stream);
+/* logit: S <= 8 segments of M logits, ld floats apart (dlogit: lddl); target_is_real: S ints on the HOST, read before the call returns.  One launch, one
+ * workgroup, fp64 sums in a fixed order.  loss[S] = mean loss of the segment, mean_logit[S], dlogit[S*M] (nullable) =
+ * scale * d loss_s / d logit.  mode 0 vanilla: BCE with logits, max(-+x, 0) + log1p(exp(-|x|)), finite at |x| = 200;  1 lsgan:
+ * (x - t)^2, t = 1 | 0;  2 hinge AS THE REFERENCE COMPUTES IT: real max(1 - x, 1), fake max(1 + x, 0) -- the real branch is not the
+ * textbook hinge max(1 - x, 0); a tie of the two operands halves the gradient, as torch.maximum does. */
+int mi_adv_loss(int S, int M, int mode, const int* target_is_real, float scale, const float* logit, int ld, float* loss,
+                float* mean_logit, float* dlogit, int lddl, void* stream);
 
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
