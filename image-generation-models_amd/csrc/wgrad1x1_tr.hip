@@ -28,6 +28,8 @@ struct W1Args {
     // small (dense) grid [N][1 << (lghw - lgw)][1 << lgw] meet pixel (2 y + gdy, 2 x + gdx) of the big [N][GH][GW] tensor (zero outside)
     int gmode;          // 0: plain 1x1; 1: P is the big (gathered) tensor; 2: Q is
     int gdy, gdx, lgw, lghw, GH, GW;
+    int tiles() const { return gx * gy; }
+    int tile_floats() const { return ni * 4 * 2048; }
 };
 __device__ __attribute__((aligned(16))) uint32_t g_w1_zero[128];      // 512 zero bytes: what a tap reads outside the big tensor
 struct W1Batch { W1Args p[MAXP]; int n; };
@@ -50,15 +52,8 @@ __device__ __forceinline__ void wgrad1_body(const W1Args& a, const int wg, uint8
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wi = wv >> 2, wj = wv & 3;
     const int ntiles = a.gx * a.gy;
-    // k-slice and tile.  The tiles of one k-slice read the same X / dY rows, and consecutive workgroup ids go to different XCDs (id % 8),
-    // each with its own L2: rank the problem's workgroups by (XCD, order on that XCD) and hand out (slice, tile) in rank order, so
-    // that a slice's tiles sit on one XCD and its rows come from HBM once (this kernel is HBM-bound: 2.2x less traffic for to_qkv).
-    int rank = wg;
-    if (a.xcd_map) {
-        const int W = ntiles * a.splits, x = (a.wg0 + wg) & 7;
-        rank = (wg - ((x - a.wg0) & 7)) >> 3;
-        for (int xx = 0; xx < x; ++xx) rank += (W - ((xx - a.wg0) & 7) + 7) >> 3;
-    }
+    // k-slice and tile, in XCD rank order (tr_common.h; this kernel is HBM-bound: 2.2x less traffic for to_qkv)
+    const int rank = a.xcd_map ? xcd_rank(a.wg0, ntiles * a.splits, wg) : wg;
     const int split = rank / ntiles, tile = rank - split * ntiles;
     const int ci0 = (tile % a.gx) * (64 * NI), co0 = (tile / a.gx) * 128;
     const int sb = split * a.sps, se = min(a.total, sb + a.sps);
@@ -189,12 +184,7 @@ __device__ __forceinline__ void wgrad1_f32_body(const W1Args& a, const int wg, u
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wi = wv >> 2, wj = wv & 3;
     const int ntiles = a.gx * a.gy;
-    int rank = wg;
-    if (a.xcd_map) {
-        const int W = ntiles * a.splits, x = (a.wg0 + wg) & 7;
-        rank = (wg - ((x - a.wg0) & 7)) >> 3;
-        for (int xx = 0; xx < x; ++xx) rank += (W - ((xx - a.wg0) & 7) + 7) >> 3;
-    }
+    const int rank = a.xcd_map ? xcd_rank(a.wg0, ntiles * a.splits, wg) : wg;
     const int split = rank / ntiles, tile = rank - split * ntiles;
     const int ci0 = (tile % a.gx) * 64, co0 = (tile / a.gx) * 128;
     const int sb = split * a.sps, se = min(a.total, sb + a.sps);
@@ -288,78 +278,46 @@ __device__ __forceinline__ void wgrad1_f32_body(const W1Args& a, const int wg, u
 __global__ __launch_bounds__(512, 1) void wgrad1x1_f32_kernel(const W1Batch b) {
     MI_PRIO_UP();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    int p = 0;
-#pragma unroll
-    for (int q = 1; q < MAXP; ++q)
-        if (q < b.n && (int)blockIdx.x >= b.p[q].wg0) p = q;
-    const W1Args& a = b.p[p];
+    const W1Args& a = b.p[batch_problem(b, (int)blockIdx.x)];
     wgrad1_f32_body(a, blockIdx.x - a.wg0, lds_raw);
 }
 
 __global__ __launch_bounds__(512, 1) void wgrad1x1_tr_kernel(const W1Batch b) {
     MI_PRIO_UP();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    int p = 0;
-#pragma unroll
-    for (int q = 1; q < MAXP; ++q)
-        if (q < b.n && (int)blockIdx.x >= b.p[q].wg0) p = q;
-    const W1Args& a = b.p[p];
+    const W1Args& a = b.p[batch_problem(b, (int)blockIdx.x)];
     const int wg = blockIdx.x - a.wg0;
     if (a.ni == 2) { if (a.q32) wgrad1_body<true, 2>(a, wg, lds_raw); else wgrad1_body<false, 2>(a, wg, lds_raw); }
     else           { if (a.q32) wgrad1_body<true, 1>(a, wg, lds_raw); else wgrad1_body<false, 1>(a, wg, lds_raw); }
 }
 
 // dW[ci][co] += (store mode: =) sum over k-slices (fixed order); grid = ((512 / IB) position groups x 64-channel regions, 4 register quads, tiles with
-// k-slices), 256 threads = G slice groups x IB = 256 / G float4 positions; each thread keeps 8 independent 16-byte loads in flight.
+// k-slices), 256 threads = G slice groups x IB = 256 / G float4 positions; each thread keeps 8 independent 16-byte loads in flight
+// (slice_sum, tr_common.h; the tail -- up to seven more -- is requested together).
 // (Round 4: it was 2 slice groups with 2 loads in flight -- a chain of 16 L2 round trips for the 64 k-slices of a to_qkv layer, 15 us per
 // launch and six launches per step.)
 template <int G>
 __global__ __launch_bounds__(256) void wgrad1x1_tr_reduce_kernel(const W1Batch b) {
     MI_PRIO_UP();
     constexpr int IB = 256 / G, PB = 512 / IB;               // positions per workgroup, workgroups per (region, quad)
-    __shared__ f32x4 red[G][IB];
-    int pi = 0;
-#pragma unroll
-    for (int q = 1; q < MAXP; ++q)
-        if (q < b.n && b.p[q].splits > 1 && (int)blockIdx.z >= b.p[q].tile0) pi = q;
-    const W1Args& a = b.p[pi];
+    const W1Args& a = b.p[reduce_problem(b, (int)blockIdx.z)];
     const int reg = blockIdx.x / PB;
     if (reg >= a.ni) return;
-    const int ntiles = a.gx * a.gy, splits = a.splits;
-    const int it = threadIdx.x % IB, grp = threadIdx.x / IB;
-    const int tt = (blockIdx.x % PB) * IB + it;
+    const int ntiles = a.gx * a.gy;
+    const int tt = (blockIdx.x % PB) * IB + threadIdx.x % IB;
     const int rq = blockIdx.y, tile = blockIdx.z - a.tile0;
     const size_t tsz = (size_t)a.ni * (4 * 2048);
     const float* p = a.ws + (size_t)tile * tsz + (size_t)reg * 8192 + (size_t)rq * 2048 + tt * 4;
-    const size_t stride = (size_t)ntiles * tsz;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    int sp = grp;
-    for (; sp + 7 * G < splits; sp += 8 * G) {
-        f32x4 v[8];
+    slice_sum<G, true>(p, (size_t)ntiles * tsz, a.splits, [&](const f32x4 s) {
+        const int wv = tt >> 6, l = tt & 63;
+        const int ci = (tile % a.gx) * (64 * a.ni) + reg * 64 + (wv >> 2) * 32 + 8 * rq + 4 * (l >> 5);
+        const int co = (tile / a.gx) * 128 + (wv & 3) * 32 + (l & 31);
+        if (co >= a.Cj) return;
+        float* out = a.dW + (size_t)ci * a.Cj + co;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const f32x4*>(p + (size_t)(sp + q * G) * stride);
-        s0 += v[0] + v[4]; s1 += v[1] + v[5]; s2 += v[2] + v[6]; s3 += v[3] + v[7];
-    }
-    {   // the tail: up to seven more, requested together
-        f32x4 v[7];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) v[q] = (sp + q * G < splits) ? *reinterpret_cast<const f32x4*>(p + (size_t)(sp + q * G) * stride) : f32x4{0.f, 0.f, 0.f, 0.f};
-        s0 += v[0] + v[4]; s1 += v[1] + v[5]; s2 += v[2] + v[6]; s3 += v[3];
-    }
-    f32x4 s = (s0 + s1) + (s2 + s3);
-    red[grp][it] = s;
-    __syncthreads();
-    if (grp != 0) return;
-#pragma unroll
-    for (int g = 1; g < G; ++g) s += red[g][it];
-    const int wv = tt >> 6, l = tt & 63;
-    const int ci = (tile % a.gx) * (64 * a.ni) + reg * 64 + (wv >> 2) * 32 + 8 * rq + 4 * (l >> 5);
-    const int co = (tile / a.gx) * 128 + (wv & 3) * 32 + (l & 31);
-    if (co >= a.Cj) return;
-    float* out = a.dW + (size_t)ci * a.Cj + co;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (ci + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
+        for (int e = 0; e < 4; ++e)
+            if (ci + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
+    });
 }
 
 bool w1_ok(const MiWgradDesc* d, int q32) {
@@ -384,49 +342,49 @@ int w1_ni(const MiWgradDesc* d) {
     return (wide >= 2 && d->Ci % 128 == 0 && d->mode != 0) ? 2 : 1;      // (exact-fp32 mode: 48 KB of raw rows per step and slot already)
 }
 
-void w1_plan(const MiWgradDesc* d, W1Args& a, long wgs) {
-    a.Ci = d->Ci; a.Cj = d->Cj; a.I1 = d->I1;
-    a.ni = w1_ni(d);
-    a.gx = d->Ci / (64 * a.ni); a.gy = (d->Cj + 127) / 128;
-    a.total = (int)((long)d->N * d->DH * d->DW / 64);
-    const int ntiles = a.gx * a.gy;
-    long splits = wgs / ntiles;
-    if (splits < 1) splits = 1;
-    if (splits > a.total) splits = a.total;
-    a.sps = (int)((a.total + splits - 1) / splits);
-    a.splits = (a.total + a.sps - 1) / a.sps;
+// The plan of a batch (tr_common.h): workgroups by the bytes a problem streams (memory-bound), k-slices, launch layout
+BatchLayout w1_plan(int n, const MiWgradDesc* d, const int* q32, W1Args* p, void* workspace) {
+    double by[MAXP]; long tiles[MAXP], wgs[MAXP];
+    for (int i = 0; i < n; ++i) {
+        W1Args& a = p[i];
+        a.Ci = d[i].Ci; a.Cj = d[i].Cj; a.I1 = d[i].I1;
+        a.ni = w1_ni(&d[i]); a.q32 = q32[i] ? 1 : 0; a.f32 = d[i].mode == 0 ? 1 : 0;
+        a.gx = a.Ci / (64 * a.ni); a.gy = (a.Cj + 127) / 128;
+        a.total = (int)((long)d[i].N * d[i].DH * d[i].DW / 64);
+        by[i] = (double)d[i].N * d[i].DH * d[i].DW * ((double)a.gy * a.Ci * (a.f32 ? 4.0 : 2.0) + (double)a.gx * a.Cj * (a.q32 ? 4.0 : 2.0));
+        tiles[i] = a.tiles();
+    }
+    balance_shares(n, by, tiles, g_w1_blocks > 0 ? g_w1_blocks : 256, wgs);
+    for (int i = 0; i < n; ++i) kslices(p[i], wgs[i]);
+    return batch_layout(n, p, workspace, [](const W1Args& a, int) {
+        static const int xcd_env = (int)mi_knob("MI_W1_XCD", 1);
+        return (xcd_env && a.tiles() > 1 && a.splits > 1) ? 1 : 0;
+    });
 }
 
-// workgroups per problem in proportion to the bytes it streams (memory-bound), every problem at least its tiles
-void w1_shares(int n, const MiWgradDesc* d, const int* q32, long* wgs) {
-    double tot = 0, by[MAXP];
-    for (int i = 0; i < n; ++i) {
-        const double tiles_ci = d[i].Ci / (64 * w1_ni(&d[i])), tiles_co = (d[i].Cj + 127) / 128;
-        by[i] = (double)d[i].N * d[i].DH * d[i].DW * (tiles_co * d[i].Ci * (d[i].mode == 0 ? 4.0 : 2.0) + tiles_ci * d[i].Cj * (q32[i] ? 4.0 : 2.0));
-        tot += by[i];
+// The launches of a planned batch whose operands are filled in.  phase: mi_debug_wgrad1x1_tr_phase
+void w1_launch(const W1Batch& b, const BatchLayout& lay, int phase, hipStream_t st) {
+    static MiPerDevice once;
+    once.run([] {
+        (void)hipFuncSetAttribute((const void*)wgrad1x1_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)wgrad1x1_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+    size_t lds = 0;           // dynamic LDS: X ring + dY ring of the largest problem (see wgrad1_body)
+    int nimax = 1;            // 64-channel regions the reduce grid covers
+    for (int i = 0; i < b.n; ++i) {
+        const W1Args& a = b.p[i];
+        const size_t ring = a.q32 ? 3 : 4;
+        const size_t l = a.f32 ? (size_t)3 * (XRAW + YRAW) : ring * ((size_t)a.ni * XSTEP + (a.q32 ? YRAW : YSTEP));
+        if (l > lds) lds = l;
+        if (a.splits > 1 && a.ni > nimax) nimax = a.ni;
     }
-    const long target = g_w1_blocks > 0 ? g_w1_blocks : 256;
-    static const int greedy = (int)mi_knob("MI_W1_BALANCE", 1);
-    if (greedy) {               // whole k-slices to whoever carries the most bytes per workgroup (tr_common.h)
-        long tiles[MAXP];
-        for (int i = 0; i < n; ++i) tiles[i] = (long)(d[i].Ci / (64 * w1_ni(&d[i]))) * ((d[i].Cj + 127) / 128);
-        balance_shares(n, by, tiles, target, wgs);
-        return;
+    if (phase != 2) {
+        if (b.p[0].f32) hipLaunchKernelGGL(wgrad1x1_f32_kernel, dim3((unsigned)lay.wgs), dim3(512), lds, st, b);
+        else hipLaunchKernelGGL(wgrad1x1_tr_kernel, dim3((unsigned)lay.wgs), dim3(512), lds, st, b);
     }
-    for (int i = 0; i < n; ++i) {
-        const long tiles = (long)(d[i].Ci / (64 * w1_ni(&d[i]))) * ((d[i].Cj + 127) / 128);
-        long w = (long)(target * by[i] / tot + 0.5);
-        w = w / tiles * tiles;
-        wgs[i] = w < tiles ? tiles : w;
+    if (phase != 1 && lay.red_tiles > 0) {
+        if (lay.max_splits >= 32) hipLaunchKernelGGL(wgrad1x1_tr_reduce_kernel<8>, dim3(16 * nimax, 4, lay.red_tiles), dim3(256), 0, st, b);
+        else hipLaunchKernelGGL(wgrad1x1_tr_reduce_kernel<2>, dim3(4 * nimax, 4, lay.red_tiles), dim3(256), 0, st, b);
     }
-}
-
-size_t w1_ws_floats(const W1Args& a) { return a.splits > 1 ? (size_t)a.splits * a.gx * a.gy * a.ni * 4 * 2048 : 0; }
-// dynamic LDS of one problem: X ring + dY ring (see wgrad1_body)
-size_t w1_lds(const W1Args& a) {
-    if (a.f32) return (size_t)3 * (XRAW + YRAW);
-    const size_t ring = a.q32 ? 3 : 4;
-    return ring * ((size_t)a.ni * XSTEP + (a.q32 ? YRAW : YSTEP));
 }
 
 }  // namespace
@@ -435,12 +393,9 @@ extern "C" int mi_conv1x1_wgrad_tr_supported(const MiWgradDesc* d, int q_is_fp32
 
 extern "C" size_t mi_conv1x1_wgrad_tr_batch_workspace(int n, const MiWgradDesc* descs, const int* q_is_fp32) {
     if (!descs || !q_is_fp32 || n < 1 || n > MAXP) return 0;
-    long wgs[MAXP];
     for (int i = 0; i < n; ++i) if (!w1_ok(&descs[i], q_is_fp32[i])) return 0;
-    w1_shares(n, descs, q_is_fp32, wgs);
-    size_t fl = 0;
-    for (int i = 0; i < n; ++i) { W1Args a; w1_plan(&descs[i], a, wgs[i]); fl += w1_ws_floats(a); }
-    return fl * sizeof(float) + 256;
+    W1Args p[MAXP];
+    return w1_plan(n, descs, q_is_fp32, p, nullptr).ws_floats * sizeof(float) + 256;
 }
 
 extern "C" int mi_debug_wgrad1x1_tr_phase(int phase) {
@@ -457,7 +412,6 @@ extern "C" int mi_conv1x1_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, con
     MI_REQUIRE((flags & ~MI_WGRAD_STORE) == 0, "unknown flag bit");
     W1Batch b{};                                          // (every field a kernel reads is defined: gmode = 0 means no gather)
     b.n = n;
-    long wgs[MAXP];
     for (int i = 0; i < n; ++i) {
         MI_REQUIRE(w1_ok(&descs[i], q_is_fp32[i]), "descriptor not supported by the LDS-DMA 1x1 weight-gradient kernel");
         MI_REQUIRE(descs[i].mode == descs[0].mode, "one numeric mode per batch");
@@ -466,40 +420,16 @@ extern "C" int mi_conv1x1_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, con
         MI_REQUIRE((((uintptr_t)P[i] | (uintptr_t)Q[i] | (uintptr_t)((P2 && P2[i]) ? P2[i] : P[i])) & 15) == 0, "operands must be 16-byte aligned");
         MI_REQUIRE(!(dbias && dbias[i]) || q_is_fp32[i], "the bias gradient is summed in the fp32 conversion pass (fp32 dY only)");
     }
-    w1_shares(n, descs, q_is_fp32, wgs);
-    size_t off = 0, lds = 0;
-    int wg = 0, tile = 0, nimax = 1, max_splits = 1;
+    const BatchLayout lay = w1_plan(n, descs, q_is_fp32, b.p, workspace);
     for (int i = 0; i < n; ++i) {
         W1Args& a = b.p[i];
-        w1_plan(&descs[i], a, wgs[i]);
         a.P = (const uint16_t*)P[i]; a.P2 = (const uint16_t*)((P2 && P2[i]) ? P2[i] : P[i]); a.Q = Q[i];
-        a.dW = dW[i]; a.dbias = dbias ? dbias[i] : nullptr; a.q32 = q_is_fp32[i] ? 1 : 0; a.f32 = descs[i].mode == 0 ? 1 : 0;
+        a.dW = dW[i]; a.dbias = dbias ? dbias[i] : nullptr;
         a.store = (flags & MI_WGRAD_STORE) ? 1 : 0;
         a.ldp = descs[i].ldp; a.ldp2 = (P2 && P2[i]) ? descs[i].ldp2 : descs[i].ldp; a.ldq = descs[i].ldq;
-        a.ws = (float*)workspace + off;
-        off += w1_ws_floats(a);
-        static const int xcd_env = (int)mi_knob("MI_W1_XCD", 1);
-        a.xcd_map = xcd_env && a.gx * a.gy > 1 && a.splits > 1;
-        a.wg0 = wg; wg += a.gx * a.gy * a.splits;
-        if (a.splits > max_splits) max_splits = a.splits;
-        a.tile0 = tile; if (a.splits > 1) { tile += a.gx * a.gy; nimax = a.ni > nimax ? a.ni : nimax; }
-        lds = w1_lds(a) > lds ? w1_lds(a) : lds;
     }
-    MI_REQUIRE(off == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= off * sizeof(float)),
-               "workspace too small (mi_conv1x1_wgrad_tr_batch_workspace)");
-    hipStream_t st = (hipStream_t)stream;
-    static MiPerDevice once;
-    once.run([] {
-        (void)hipFuncSetAttribute((const void*)wgrad1x1_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)wgrad1x1_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    if (g_w1_phase != 2) {
-        if (descs[0].mode == 0) hipLaunchKernelGGL(wgrad1x1_f32_kernel, dim3((unsigned)wg), dim3(512), lds, st, b);
-        else hipLaunchKernelGGL(wgrad1x1_tr_kernel, dim3((unsigned)wg), dim3(512), lds, st, b);
-    }
-    if (g_w1_phase != 1 && tile > 0) {
-        if (max_splits >= 32) hipLaunchKernelGGL(wgrad1x1_tr_reduce_kernel<8>, dim3(16 * nimax, 4, tile), dim3(256), 0, st, b);
-        else hipLaunchKernelGGL(wgrad1x1_tr_reduce_kernel<2>, dim3(4 * nimax, 4, tile), dim3(256), 0, st, b);
-    }
+    MI_REQUIRE(ws_ok(lay.ws_floats, workspace, ws_bytes), "workspace too small (mi_conv1x1_wgrad_tr_batch_workspace)");
+    w1_launch(b, lay, g_w1_phase, (hipStream_t)stream);
     MI_LAUNCH_CHECK();
     return 0;
 }
@@ -522,87 +452,57 @@ bool s2f_ok(const MiWgradDesc* d) {
     if (d->GH != 2 * d->DH || d->GW != 2 * d->DW || (d->DH & (d->DH - 1)) || (d->DW & (d->DW - 1))) return false;
     return ((long)d->N * d->DH * d->DW) % 64 == 0;
 }
-MiWgradDesc s2f_tap_desc(const MiWgradDesc* d) {          // the dense 1x1 problem one tap is planned as
-    MiWgradDesc t = *d;
-    t.KH = t.KW = 1; t.pad = 0; t.stride = 1; t.gather_i = 1; t.GH = d->DH; t.GW = d->DW;
-    return t;
-}
 int s2f_groups(int ntap, int* first, int* count) {          // taps per launch: 9 -> 5 + 4, 16 -> 8 + 8
     const int ng = (ntap + MAXP - 1) / MAXP;
     int t0 = 0;
     for (int g = 0; g < ng; ++g) { first[g] = t0; count[g] = (ntap - t0 + (ng - g) - 1) / (ng - g); t0 += count[g]; }
     return ng;
 }
-size_t s2f_group_ws(const MiWgradDesc* d, int n) {
-    const MiWgradDesc t = s2f_tap_desc(d);
-    MiWgradDesc ds[MAXP]; int q32[MAXP]; long wgs[MAXP];
+// a group of n taps: each is planned as the dense 1x1 problem over the small grid
+BatchLayout s2f_group_plan(const MiWgradDesc* d, int n, W1Args* p, void* workspace) {
+    MiWgradDesc t = *d;
+    t.KH = t.KW = 1; t.pad = 0; t.stride = 1; t.gather_i = 1; t.GH = d->DH; t.GW = d->DW;
+    MiWgradDesc ds[MAXP]; int q32[MAXP];
     for (int i = 0; i < n; ++i) { ds[i] = t; q32[i] = 1; }
-    w1_shares(n, ds, q32, wgs);
+    return w1_plan(n, ds, q32, p, workspace);
+}
+// floats of the one workspace the tap groups use in turn.  The second group can need more than the first (9 taps = 5 + 4: four
+// problems get more k-slices each than five)
+size_t s2f_ws_floats(const MiWgradDesc* d) {
+    int first[4], count[4];
+    const int ng = s2f_groups(d->KH * d->KW, first, count);
     size_t fl = 0;
-    for (int i = 0; i < n; ++i) { W1Args a{}; w1_plan(&t, a, wgs[i]); fl += w1_ws_floats(a); }
+    for (int g = 0; g < ng; ++g) { W1Args p[MAXP]; const size_t f = s2f_group_plan(d, count[g], p, nullptr).ws_floats; fl = f > fl ? f : fl; }
     return fl;
 }
 }  // namespace
 extern "C" int mi_conv_s2_wgrad_f32_supported(const MiWgradDesc* d) { return s2f_ok(d) ? 1 : 0; }
 extern "C" size_t mi_conv_s2_wgrad_f32_workspace(const MiWgradDesc* d) {
-    if (!s2f_ok(d)) return 0;
-    int first[4], count[4];
-    const int ng = s2f_groups(d->KH * d->KW, first, count);
-    size_t fl = 0;
-    for (int g = 0; g < ng; ++g) { const size_t f = s2f_group_ws(d, count[g]); fl = f > fl ? f : fl; }
-    return fl * sizeof(float) + 256;
+    return s2f_ok(d) ? s2f_ws_floats(d) * sizeof(float) + 256 : 0;
 }
 extern "C" int mi_conv_s2_wgrad_f32(const MiWgradDesc* d, const float* P, const float* Q, float* dW, void* workspace, size_t ws_bytes, void* stream) {
     MI_REQUIRE(s2f_ok(d), "descriptor not supported (exact-fp32 mode, 3x3 or 4x4, stride 2, pad 1, one source, Ci % 64, Cj % 32, power-of-two small grid)");
     MI_REQUIRE(P && Q && dW && ((((uintptr_t)P | (uintptr_t)Q) & 15) == 0), "null or misaligned operand");
-    hipStream_t st = (hipStream_t)stream;
-    static MiPerDevice once;
-    once.run([] { (void)hipFuncSetAttribute((const void*)wgrad1x1_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    const MiWgradDesc t = s2f_tap_desc(d);
     int lgw = 0, lgh = 0;
     while ((1 << lgw) < d->DW) ++lgw;
     while ((1 << lgh) < d->DH) ++lgh;
+    // the largest group's workspace is required before the first launch: a call that is refused must not have added the first group's taps to dW
+    MI_REQUIRE(ws_ok(s2f_ws_floats(d), workspace, ws_bytes), "workspace too small (mi_conv_s2_wgrad_f32_workspace)");
     int first[4], count[4];
     const int ng = s2f_groups(d->KH * d->KW, first, count);
-    // every tap group's workspace is checked before the first launch: the second group can need more than the first (9 taps = 5 + 4:
-    // four problems get more k-slices each than five), and a call that is refused must not have added the first group's taps to dW
-    size_t need = 0;
-    for (int g = 0; g < ng; ++g) { const size_t f = s2f_group_ws(d, count[g]); need = f > need ? f : need; }
-    MI_REQUIRE(need == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= need * sizeof(float)),
-               "workspace too small (mi_conv_s2_wgrad_f32_workspace)");
     for (int g = 0; g < ng; ++g) {
-        const int n = count[g];
-        MiWgradDesc ds[MAXP]; int q32[MAXP]; long wgs[MAXP];
-        for (int i = 0; i < n; ++i) { ds[i] = t; q32[i] = 1; }
-        w1_shares(n, ds, q32, wgs);
-        W1Batch b{};                                          // (every field a kernel reads is defined: gmode = 0 means no gather)
-        b.n = n;
-        size_t off = 0, lds = 0;
-        int wg = 0, tile = 0, max_splits = 1;
-        for (int i = 0; i < n; ++i) {
+        W1Batch b{};                                          // (every field a kernel reads is defined)
+        b.n = count[g];
+        const BatchLayout lay = s2f_group_plan(d, b.n, b.p, workspace);
+        for (int i = 0; i < b.n; ++i) {
             const int tap = first[g] + i, ky = tap / d->KW, kx = tap % d->KW;
             W1Args& a = b.p[i];
-            a = W1Args{};
-            w1_plan(&t, a, wgs[i]);
             a.P = (const uint16_t*)P; a.P2 = (const uint16_t*)P; a.Q = Q;
-            a.dW = dW + (size_t)tap * d->Ci * d->Cj; a.dbias = nullptr; a.q32 = 1; a.f32 = 1;
+            a.dW = dW + (size_t)tap * d->Ci * d->Cj;
             a.ldp = d->ldp; a.ldp2 = d->ldp; a.ldq = d->ldq;
-            a.ws = (float*)workspace + off;
-            off += w1_ws_floats(a);
-            a.xcd_map = a.gx * a.gy > 1 && a.splits > 1;
-            a.wg0 = wg; wg += a.gx * a.gy * a.splits;
-            if (a.splits > max_splits) max_splits = a.splits;
-            a.tile0 = tile; if (a.splits > 1) tile += a.gx * a.gy;
             a.gmode = d->gather_i ? 1 : 2; a.gdy = ky - d->pad; a.gdx = kx - d->pad; a.lgw = lgw; a.lghw = lgw + lgh; a.GH = d->GH; a.GW = d->GW;
-            lds = w1_lds(a) > lds ? w1_lds(a) : lds;
         }
-        MI_REQUIRE(off == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= off * sizeof(float)),
-                   "workspace too small (mi_conv_s2_wgrad_f32_workspace)");
-        hipLaunchKernelGGL(wgrad1x1_f32_kernel, dim3((unsigned)wg), dim3(512), lds, st, b);
-        if (tile > 0) {
-            if (max_splits >= 32) hipLaunchKernelGGL(wgrad1x1_tr_reduce_kernel<8>, dim3(16, 4, tile), dim3(256), 0, st, b);
-            else hipLaunchKernelGGL(wgrad1x1_tr_reduce_kernel<2>, dim3(4, 4, tile), dim3(256), 0, st, b);
-        }
+        w1_launch(b, lay, 0, (hipStream_t)stream);
         MI_LAUNCH_CHECK();
     }
     return 0;

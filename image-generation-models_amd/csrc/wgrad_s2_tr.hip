@@ -18,8 +18,8 @@
 //     32 x 32 x 9 = 144 accumulators, 36 MFMAs per step.
 //   * 4x4: 16 taps would need 256 accumulators per wave, so a workgroup takes ONE column plane (8 taps, 128 accumulators, 16 KB of
 //     big rows per step); the two planes are separate tiles.
-// A step's DMA is requested one step ahead (ring of 3 big slots, 2 small slots).  k-slices, partial tiles in register order,
-// fixed-order reduce and CU shares proportional to the work are as in wgrad_tr.hip.
+// A step's DMA is requested one step ahead (ring of 3 big slots, 2 small slots).  k-slices, partial tiles in register order, the
+// fixed-order reduce and the workgroups' shares by work are those of wgrad_tr.hip (planner and slice sum: tr_common.h).
 #include "tr_common.h"
 
 namespace {
@@ -33,6 +33,8 @@ struct S2Args {
     int gx, gy, ntiles;                     // big-channel tiles (64), small-channel tiles (128), tiles incl. the plane factor
     int wg0, tile0, xcd_map;
     int store;                              // != 0: dW = result instead of dW += result (MI_WGRAD_STORE)
+    int tiles() const { return ntiles; }
+    int tile_floats() const { return (KS == 3 ? 36 : 32) * 2048; }
 };
 struct S2Batch { S2Args p[MAXP]; int n; };
 
@@ -84,13 +86,8 @@ __device__ __forceinline__ void wgrad_s2_body(const S2Args& a, const int wg, uin
     const int t = threadIdx.x, l = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wi = wv >> 2, wj = wv & 3;             // 2 big-channel halves x 4 small-channel quarters
-    // (k-slice, tile) in XCD rank order: a slice's tiles (they read the same rows) run on one XCD / one L2 -- see wgrad1x1_tr.hip
-    int rank = wg;
-    if (a.xcd_map) {
-        const int Wg = a.ntiles * a.splits, x = (a.wg0 + wg) & 7;
-        rank = (wg - ((x - a.wg0) & 7)) >> 3;
-        for (int xx = 0; xx < x; ++xx) rank += (Wg - ((xx - a.wg0) & 7) + 7) >> 3;
-    }
+    // (k-slice, tile) in XCD rank order: a slice's tiles (they read the same rows) run on one XCD / one L2 (tr_common.h)
+    const int rank = a.xcd_map ? xcd_rank(a.wg0, a.ntiles * a.splits, wg) : wg;
     const int split = rank / a.ntiles, tile = rank - split * a.ntiles;
     const int tb = tile % a.gx, tsm = (tile / a.gx) % a.gy, q = tile / (a.gx * a.gy);      // q: column plane of a 4x4 tile (0 even, 1 odd)
     const int cb0 = tb * 64, cs0 = tsm * 128;
@@ -255,11 +252,7 @@ __device__ __forceinline__ void wgrad_s2_body(const S2Args& a, const int wg, uin
 __global__ __launch_bounds__(512, 1) void wgrad_s2_tr_kernel(const S2Batch b) {
     MI_PRIO_UP();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    int p = 0;
-#pragma unroll
-    for (int k = 1; k < MAXP; ++k)
-        if (k < b.n && (int)blockIdx.x >= b.p[k].wg0) p = k;
-    const S2Args& a = b.p[p];
+    const S2Args& a = b.p[batch_problem(b, (int)blockIdx.x)];
     const int wg = blockIdx.x - a.wg0;
     if (a.KS == 3) {
         switch (a.w) {
@@ -277,54 +270,34 @@ __global__ __launch_bounds__(512, 1) void wgrad_s2_tr_kernel(const S2Batch b) {
 }
 
 // dW += (store mode: =) sum over k-slices of the partial tiles (fixed order).  grid = (position groups, slots of the largest problem, tiles of all
-// problems that have k-slices); a workgroup = G slice groups x (256 / G) float4 positions of one slot.
+// problems that have k-slices); a workgroup = G slice groups x (256 / G) float4 positions of one slot (slice_sum, tr_common.h).
 template <int G>
 __global__ __launch_bounds__(256) void wgrad_s2_reduce_kernel(const S2Batch b) {
     MI_PRIO_UP();
     constexpr int IB = 256 / G;
-    __shared__ f32x4 red[G][IB];
-    int pi = 0;
-#pragma unroll
-    for (int k = 1; k < MAXP; ++k)
-        if (k < b.n && b.p[k].splits > 1 && (int)blockIdx.z >= b.p[k].tile0) pi = k;
-    const S2Args& a = b.p[pi];
+    const S2Args& a = b.p[reduce_problem(b, (int)blockIdx.z)];
     const bool swap = a.KS == 4;
     const int nslot = (a.KS == 3 ? 9 : 8) * 4;
     const int slot = blockIdx.y;
     if (slot >= nslot) return;
-    const int it = threadIdx.x % IB, grp = threadIdx.x / IB;
-    const int tt = blockIdx.x * IB + it;                       // thread of the producing workgroup
+    const int tt = blockIdx.x * IB + threadIdx.x % IB;         // thread of the producing workgroup
     const int tile = blockIdx.z - a.tile0;
     const size_t tile_fl = (size_t)nslot * 2048;
     const float* p = a.ws + (size_t)tile * tile_fl + (size_t)slot * 2048 + tt * 4;
-    const size_t stride = (size_t)a.ntiles * tile_fl;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    int sp = grp;
-    for (; sp + 7 * G < a.splits; sp += 8 * G) {
-        f32x4 v[8];
+    slice_sum<G, false>(p, (size_t)a.ntiles * tile_fl, a.splits, [&](const f32x4 s) {
+        const int wv = tt >> 6, l = tt & 63, wi = wv >> 2, wj = wv & 3;
+        const int rq = slot & 3, ta = slot >> 2;
+        const int tb = tile % a.gx, tsm = (tile / a.gx) % a.gy, q = tile / (a.gx * a.gy);
+        const int cb0 = tb * 64, cs0 = tsm * 128;
+        const int row = (swap ? cs0 + wj * 32 : cb0 + wi * 32) + 8 * rq + 4 * (l >> 5);
+        const int col = (swap ? cb0 + wi * 32 : cs0 + wj * 32) + (l & 31);
+        const int tap = a.KS == 3 ? ta : (ta >> 1) * 4 + (q ? ((ta & 1) ? 2 : 0) : ((ta & 1) ? 3 : 1));
+        if (col >= a.Cj) return;
+        float* out = a.dW + ((size_t)tap * a.Ci + row) * a.Cj + col;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const f32x4*>(p + (size_t)(sp + k * G) * stride);
-        s0 += v[0] + v[4]; s1 += v[1] + v[5]; s2 += v[2] + v[6]; s3 += v[3] + v[7];
-    }
-    for (; sp < a.splits; sp += G) s0 += *reinterpret_cast<const f32x4*>(p + (size_t)sp * stride);
-    f32x4 s = (s0 + s1) + (s2 + s3);
-    red[grp][it] = s;
-    __syncthreads();
-    if (grp != 0) return;
-#pragma unroll
-    for (int g = 1; g < G; ++g) s += red[g][it];
-    const int wv = tt >> 6, l = tt & 63, wi = wv >> 2, wj = wv & 3;
-    const int rq = slot & 3, ta = slot >> 2;
-    const int tb = tile % a.gx, tsm = (tile / a.gx) % a.gy, q = tile / (a.gx * a.gy);
-    const int cb0 = tb * 64, cs0 = tsm * 128;
-    const int row = (swap ? cs0 + wj * 32 : cb0 + wi * 32) + 8 * rq + 4 * (l >> 5);
-    const int col = (swap ? cb0 + wi * 32 : cs0 + wj * 32) + (l & 31);
-    const int tap = a.KS == 3 ? ta : (ta >> 1) * 4 + (q ? ((ta & 1) ? 2 : 0) : ((ta & 1) ? 3 : 1));
-    if (col >= a.Cj) return;
-    float* out = a.dW + ((size_t)tap * a.Ci + row) * a.Cj + col;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (row + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
+        for (int e = 0; e < 4; ++e)
+            if (row + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
+    });
 }
 
 bool s2_ok(const MiWgradDesc* d) {
@@ -341,12 +314,8 @@ bool s2_ok(const MiWgradDesc* d) {
     return true;
 }
 
-long s2_target() {
-    static const long env_target = mi_knob("MI_WS2_BLOCKS", 256);
-    return env_target;
-}
-
-void s2_plan(const MiWgradDesc* d, S2Args& a, long wgs) {
+// tiles and steps of one problem
+void s2_geom(const MiWgradDesc* d, S2Args& a) {
     a.w = d->DW; a.h = d->DH; a.KS = d->KH; a.Ci = d->Ci; a.Cj = d->Cj;
     a.Cb = d->gather_i ? d->Ci : d->Cj; a.Cs = d->gather_i ? d->Cj : d->Ci;
     a.ldb = d->gather_i ? d->ldp : d->ldq; a.lds_ = d->gather_i ? d->ldq : d->ldp;
@@ -354,42 +323,29 @@ void s2_plan(const MiWgradDesc* d, S2Args& a, long wgs) {
     a.gx = a.Cb / 64; a.gy = (a.Cs + 127) / 128;
     a.ntiles = a.gx * a.gy * (a.KS == 4 ? 2 : 1);
     a.total = (int)((long)d->N * d->DH * d->DW / 64);
-    long splits = wgs / a.ntiles;
-    if (splits < 1) splits = 1;
-    if (splits > a.total) splits = a.total;
-    a.sps = (int)((a.total + splits - 1) / splits);
-    a.splits = (a.total + a.sps - 1) / a.sps;
 }
 
-long s2_tiles(const MiWgradDesc* d) {
-    const int Cb = d->gather_i ? d->Ci : d->Cj, Cs = d->gather_i ? d->Cj : d->Ci;
-    return (long)(Cb / 64) * ((Cs + 127) / 128) * (d->KH == 4 ? 2 : 1);
-}
-
-void s2_shares(int n, const MiWgradDesc* d, long* wgs) {
-    double tot = 0, fl[MAXP];
-    for (int i = 0; i < n; ++i) { fl[i] = (double)d[i].N * d[i].DH * d[i].DW * d[i].Ci * d[i].Cj * d[i].KH * d[i].KW; tot += fl[i]; }
-    const long target = s2_target();
-    static const int greedy = (int)mi_knob("MI_WS2_BALANCE", 1);
-    if (greedy) {
-        long tiles[MAXP];
-        for (int i = 0; i < n; ++i) tiles[i] = s2_tiles(&d[i]);
-        balance_shares(n, fl, tiles, target, wgs);
-        return;
-    }
+// The plan of a batch (tr_common.h): workgroups by MFMA work (N*h*w*Ci*Cj*k*k), k-slices, launch layout
+BatchLayout s2_plan(int n, const MiWgradDesc* d, S2Args* p, void* workspace) {
+    double fl[MAXP]; long tiles[MAXP], wgs[MAXP];
     for (int i = 0; i < n; ++i) {
-        const long tiles = s2_tiles(&d[i]);
-        long w = (long)(target * fl[i] / tot + 0.5);
-        w = w / tiles * tiles;
-        wgs[i] = w < tiles ? tiles : w;
+        s2_geom(&d[i], p[i]);
+        fl[i] = (double)d[i].N * d[i].DH * d[i].DW * d[i].Ci * d[i].Cj * d[i].KH * d[i].KW;
+        tiles[i] = p[i].tiles();
     }
+    static const long target = mi_knob("MI_WS2_BLOCKS", 256);
+    balance_shares(n, fl, tiles, target, wgs);
+    for (int i = 0; i < n; ++i) kslices(p[i], wgs[i]);
+    return batch_layout(n, p, workspace, [](const S2Args& a, int) {
+        static const int xcd_env = (int)mi_knob("MI_WS2_XCD", 1);
+        return (xcd_env && a.tiles() > 1 && a.splits > 1) ? 1 : 0;
+    });
 }
 
 size_t s2_lds(const S2Args& a) {
     const size_t browb = (size_t)(a.KS == 3 ? 2 : 1) * (a.w / 8) * 1024;
     return browb + 3 * (2 * (64 / a.w)) * browb + 2 * 64 * 256;
 }
-size_t s2_ws_floats(const S2Args& a) { return a.splits > 1 ? (size_t)a.splits * a.ntiles * (a.KS == 3 ? 36 : 32) * 2048 : 0; }
 
 int g_ws2_phase = 0;
 
@@ -399,12 +355,9 @@ extern "C" int mi_conv_s2_wgrad_tr_supported(const MiWgradDesc* d) { return (d &
 
 extern "C" size_t mi_conv_s2_wgrad_tr_batch_workspace(int n, const MiWgradDesc* descs) {
     if (!descs || n < 1 || n > MAXP) return 0;
-    long wgs[MAXP];
     for (int i = 0; i < n; ++i) if (!s2_ok(&descs[i])) return 0;
-    s2_shares(n, descs, wgs);
-    size_t fl = 0;
-    for (int i = 0; i < n; ++i) { S2Args a; s2_plan(&descs[i], a, wgs[i]); fl += s2_ws_floats(a); }
-    return fl * sizeof(float) + 256;
+    S2Args p[MAXP];
+    return s2_plan(n, descs, p, nullptr).ws_floats * sizeof(float) + 256;
 }
 
 extern "C" int mi_debug_wgrad_s2_tr_phase(int phase) {
@@ -419,41 +372,30 @@ extern "C" int mi_conv_s2_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, con
     MI_REQUIRE((flags & ~MI_WGRAD_STORE) == 0, "unknown flag bit");
     S2Batch b;
     b.n = n;
-    long wgs[MAXP];
     for (int i = 0; i < n; ++i) {
         MI_REQUIRE(s2_ok(&descs[i]), "descriptor not supported by the stride-2 LDS-DMA weight-gradient kernel (use mi_conv_wgrad)");
         MI_REQUIRE(P[i] && Q[i] && dW[i], "null operand");
         MI_REQUIRE((((uintptr_t)P[i] | (uintptr_t)Q[i]) & 15) == 0, "operands must be 16-byte aligned");
     }
-    s2_shares(n, descs, wgs);
-    size_t off = 0, lds = 0;
-    int wg = 0, tile = 0, max_splits = 1;
+    const BatchLayout lay = s2_plan(n, descs, b.p, workspace);
+    size_t lds = 0;
     for (int i = 0; i < n; ++i) {
         S2Args& a = b.p[i];
-        s2_plan(&descs[i], a, wgs[i]);
         a.B = (const uint16_t*)(descs[i].gather_i ? P[i] : Q[i]);
         a.S = (const uint16_t*)(descs[i].gather_i ? Q[i] : P[i]);
         a.dW = dW[i]; a.store = (flags & MI_WGRAD_STORE) ? 1 : 0;
-        a.ws = (float*)workspace + off;
-        off += s2_ws_floats(a);
-        static const int xcd_env = (int)mi_knob("MI_WS2_XCD", 1);
-        a.xcd_map = xcd_env && a.ntiles > 1 && a.splits > 1;
-        a.wg0 = wg; wg += a.ntiles * a.splits;
-        a.tile0 = tile; if (a.splits > 1) tile += a.ntiles;
-        if (a.splits > max_splits) max_splits = a.splits;
         const size_t l = s2_lds(a);
         if (l > lds) lds = l;
     }
-    MI_REQUIRE(off == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= off * sizeof(float)),
-               "workspace too small (mi_conv_s2_wgrad_tr_batch_workspace)");
+    MI_REQUIRE(ws_ok(lay.ws_floats, workspace, ws_bytes), "workspace too small (mi_conv_s2_wgrad_tr_batch_workspace)");
     hipStream_t st = (hipStream_t)stream;
     static MiPerDevice once;
     once.run([] {
         (void)hipFuncSetAttribute((const void*)wgrad_s2_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    if (g_ws2_phase != 2) hipLaunchKernelGGL(wgrad_s2_tr_kernel, dim3((unsigned)wg), dim3(512), lds, st, b);
-    if (g_ws2_phase != 1 && tile > 0) {
-        if (max_splits >= 64) hipLaunchKernelGGL(wgrad_s2_reduce_kernel<8>, dim3(16, 36, tile), dim3(256), 0, st, b);
-        else hipLaunchKernelGGL(wgrad_s2_reduce_kernel<2>, dim3(4, 36, tile), dim3(256), 0, st, b);
+    if (g_ws2_phase != 2) hipLaunchKernelGGL(wgrad_s2_tr_kernel, dim3((unsigned)lay.wgs), dim3(512), lds, st, b);
+    if (g_ws2_phase != 1 && lay.red_tiles > 0) {
+        if (lay.max_splits >= 64) hipLaunchKernelGGL(wgrad_s2_reduce_kernel<8>, dim3(16, 36, lay.red_tiles), dim3(256), 0, st, b);
+        else hipLaunchKernelGGL(wgrad_s2_reduce_kernel<2>, dim3(4, 36, lay.red_tiles), dim3(256), 0, st, b);
     }
     MI_LAUNCH_CHECK();
     return 0;

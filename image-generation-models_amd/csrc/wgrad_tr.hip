@@ -55,6 +55,23 @@ extern "C" int mi_debug_wtr_steps(unsigned long long* host_out) {
 
 namespace {
 
+struct TrArgs {
+    const uint16_t* P; const uint16_t* P2; const uint16_t* Q;
+    float* ws;          // this problem's partial tiles (splits > 1)
+    float* dW;          // [3][3][Ci][Cj], accumulated into directly when splits == 1
+    int W, H, Ci, Cj, I1, ldp, ldp2, ldq;
+    int total;          // steps of 64 pixels over the whole batch: N*H*W / 64
+    int sps, splits;    // steps per k-slice, k-slices
+    int gx, gy;         // ci tiles (64), co tiles (128)
+    int wg0;            // first workgroup of this problem in the launch
+    int tile0;          // first tile of this problem in the reduce launch
+    int xcd_map;        // workgroup -> (k-slice, tile) such that the tiles of a k-slice share an XCD
+    int store;          // != 0: dW = result instead of dW += result (MI_WGRAD_STORE)
+    int tiles() const { return gx * gy; }
+    static constexpr int tile_floats() { return 36 * 2048; }
+};
+struct TrBatch { TrArgs p[MAXP]; int n; };
+
 // W = image width (8, 16, 32 or 64); a step is TR = 64 / W rows of one image (H % TR == 0).  wg = workgroup index within the problem.
 template <int W>
 __device__ __forceinline__ void wgrad_tr_body(const TrArgs& a, const int wg, uint8_t* lds_raw) {
@@ -281,11 +298,7 @@ __device__ __forceinline__ void wgrad_tr_body(const TrArgs& a, const int wg, uin
 __global__ __launch_bounds__(512, 1) void wgrad_tr_kernel(const TrBatch b) {
     MI_PRIO_UP();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    int p = 0;
-#pragma unroll
-    for (int q = 1; q < MAXP; ++q)
-        if (q < b.n && (int)blockIdx.x >= b.p[q].wg0) p = q;
-    const TrArgs& a = b.p[p];
+    const TrArgs& a = b.p[batch_problem(b, (int)blockIdx.x)];
     const int wg = blockIdx.x - a.wg0;
     switch (a.W) {
         case 8:  wgrad_tr_body<8>(a, wg, lds_raw); break;
@@ -450,11 +463,7 @@ __device__ __forceinline__ void wgrad_tr32_body(const TrArgs& a, const int wg, u
 __global__ __launch_bounds__(512, 1) void wgrad_tr32_kernel(const TrBatch b) {
     MI_PRIO_UP();
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
-    int p = 0;
-#pragma unroll
-    for (int q = 1; q < MAXP; ++q)
-        if (q < b.n && (int)blockIdx.x >= b.p[q].wg0) p = q;
-    const TrArgs& a = b.p[p];
+    const TrArgs& a = b.p[batch_problem(b, (int)blockIdx.x)];
     const int wg = blockIdx.x - a.wg0;
     switch (a.W) {
         case 8:  wgrad_tr32_body<8>(a, wg, lds_raw); break;
@@ -465,48 +474,27 @@ __global__ __launch_bounds__(512, 1) void wgrad_tr32_kernel(const TrBatch b) {
 }
 
 // dW[tap][ci][co] += (store mode: =) sum over k-slices of the partial tiles (fixed order).  grid = (2G position groups, 36 slots, tiles of all
-// problems that have k-slices); a workgroup = G slice groups x (256 / G) float4 positions of one slot; each thread keeps 8
-// independent 16-byte loads in flight.
+// problems that have k-slices); a workgroup = G slice groups x (256 / G) float4 positions of one slot (slice_sum, tr_common.h).
 template <int G>
 __global__ __launch_bounds__(256) void wgrad_tr_reduce_kernel(const TrBatch b) {
     MI_PRIO_UP();
     constexpr int IB = 256 / G;
-    __shared__ f32x4 red[G][IB];
-    int pi = 0;
-#pragma unroll
-    for (int q = 1; q < MAXP; ++q)
-        if (q < b.n && b.p[q].splits > 1 && (int)blockIdx.z >= b.p[q].tile0) pi = q;
-    const TrArgs& a = b.p[pi];
-    const int ntiles = a.gx * a.gy, splits = a.splits;
-    const int it = threadIdx.x % IB, grp = threadIdx.x / IB;
-    const int tt = blockIdx.x * IB + it;                       // thread of the producing workgroup
+    const TrArgs& a = b.p[reduce_problem(b, (int)blockIdx.z)];
+    const int ntiles = a.gx * a.gy;
+    const int tt = blockIdx.x * IB + threadIdx.x % IB;         // thread of the producing workgroup
     const int slot = blockIdx.y, tile = blockIdx.z - a.tile0;
     const float* p = a.ws + (size_t)tile * (36 * 2048) + (size_t)slot * 2048 + tt * 4;
-    const size_t stride = (size_t)ntiles * (36 * 2048);
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    int sp = grp;
-    for (; sp + 7 * G < splits; sp += 8 * G) {
-        f32x4 v[8];
+    slice_sum<G, false>(p, (size_t)ntiles * (36 * 2048), a.splits, [&](const f32x4 s) {
+        const int wv = tt >> 6, l = tt & 63;
+        const int rq = slot & 3, tap = slot >> 2;
+        const int ci = (tile % a.gx) * 64 + (wv >> 2) * 32 + 8 * rq + 4 * (l >> 5);
+        const int co = (tile / a.gx) * 128 + (wv & 3) * 32 + (l & 31);
+        if (co >= a.Cj) return;
+        float* out = a.dW + ((size_t)tap * a.Ci + ci) * a.Cj + co;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = *reinterpret_cast<const f32x4*>(p + (size_t)(sp + q * G) * stride);
-        s0 += v[0] + v[4]; s1 += v[1] + v[5]; s2 += v[2] + v[6]; s3 += v[3] + v[7];
-    }
-    for (; sp < splits; sp += G) s0 += *reinterpret_cast<const f32x4*>(p + (size_t)sp * stride);
-    f32x4 s = (s0 + s1) + (s2 + s3);
-    red[grp][it] = s;
-    __syncthreads();
-    if (grp != 0) return;
-#pragma unroll
-    for (int g = 1; g < G; ++g) s += red[g][it];
-    const int wv = tt >> 6, l = tt & 63;
-    const int rq = slot & 3, tap = slot >> 2;
-    const int ci = (tile % a.gx) * 64 + (wv >> 2) * 32 + 8 * rq + 4 * (l >> 5);
-    const int co = (tile / a.gx) * 128 + (wv & 3) * 32 + (l & 31);
-    if (co >= a.Cj) return;
-    float* out = a.dW + ((size_t)tap * a.Ci + ci) * a.Cj + co;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (ci + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
+        for (int e = 0; e < 4; ++e)
+            if (ci + e < a.Ci) wg_put(out + (size_t)e * a.Cj, s[e], a.store);
+    });
 }
 
 bool tr_ok(const MiWgradDesc* d) {
@@ -529,42 +517,34 @@ long tr_target() {
     return g_wtr_blocks > 0 ? g_wtr_blocks : env_target;
 }
 
-// k-slices of one problem that is given `wgs` workgroups
-void tr_plan(const MiWgradDesc* d, TrArgs& a, long wgs) {
+// tiles and steps of one problem
+void tr_geom(const MiWgradDesc* d, TrArgs& a) {
     a.W = d->DW; a.H = d->DH; a.Ci = d->Ci; a.Cj = d->Cj; a.I1 = d->I1;
     a.gx = d->Ci / 64; a.gy = (d->Cj + 127) / 128;
     a.total = (int)((long)d->N * d->DH * d->DW / 64);
-    const int ntiles = a.gx * a.gy;
-    long splits = wgs / ntiles;
-    if (splits < 1) splits = 1;
-    if (splits > a.total) splits = a.total;
-    a.sps = (int)((a.total + splits - 1) / splits);
-    a.splits = (a.total + a.sps - 1) / a.sps;
 }
 
-// workgroups per problem in proportion to the MFMA work (N*H*W*Ci*Cj rounded up to whole tiles), every problem at least its tiles
-void tr_shares(int n, const MiWgradDesc* d, long* wgs) {
-    double fl[MAXP]; long tiles[MAXP];
+// The plan of a batch (tr_common.h): workgroups by MFMA work (N*H*W*Ci*Cj, Cj rounded up to whole tiles), k-slices, launch layout
+BatchLayout tr_plan(int n, const MiWgradDesc* d, TrArgs* p, void* workspace) {
+    double fl[MAXP]; long tiles[MAXP], wgs[MAXP];
     for (int i = 0; i < n; ++i) {
+        tr_geom(&d[i], p[i]);
         fl[i] = (double)d[i].N * d[i].DH * d[i].DW * d[i].Ci * ((d[i].Cj + 127) / 128 * 128);
-        tiles[i] = (long)(d[i].Ci / 64) * ((d[i].Cj + 127) / 128);
+        tiles[i] = p[i].tiles();
     }
-    static const int greedy = (int)mi_knob("MI_WTR_BALANCE", 1);
-    const long target = tr_target();
-    if (greedy) { balance_shares(n, fl, tiles, target, wgs); return; }
-    double tot = 0;
-    for (int i = 0; i < n; ++i) tot += fl[i];
-    for (int i = 0; i < n; ++i) {
-        long w = (long)(target * fl[i] / tot + 0.5);
-        w = w / tiles[i] * tiles[i];                            // whole k-slices
-        wgs[i] = w < tiles[i] ? tiles[i] : w;
-    }
+    balance_shares(n, fl, tiles, tr_target(), wgs);
+    for (int i = 0; i < n; ++i) kslices(p[i], wgs[i]);
+    // the two forms of wgrad_tr_body's map need the problem to start on XCD 0 and the slices to divide the 8 XCDs (1) or the other way round (2)
+    return batch_layout(n, p, workspace, [](const TrArgs& a, int wg0) {
+        static const int xcd_env = (int)mi_knob("MI_WTR_XCD", 2);
+        if (!xcd_env || a.tiles() <= 1 || wg0 % 8) return 0;
+        if (a.splits % 8 == 0) return 1;
+        return (xcd_env > 1 && a.splits < 8 && 8 % a.splits == 0 && a.tiles() % (8 / a.splits) == 0) ? 2 : 0;
+    });
 }
 
 size_t tr_lds(int W) { return (size_t)((W / 8 + 2) * 1024) * (1 + 4 * (64 / W)) + 3 * 64 * 256; }
 size_t tr32_lds(int W) { return (size_t)((W + 2) * 256) * (1 + 4 * (64 / W)) + 2 * 64 * 512; }
-
-size_t tr_ws_floats(const TrArgs& a) { return a.splits > 1 ? (size_t)a.splits * a.gx * a.gy * 36 * 2048 : 0; }
 
 }  // namespace
 
@@ -573,18 +553,15 @@ extern "C" int mi_conv3x3_wgrad_tr_supported(const MiWgradDesc* d) { return (d &
 // Scratch bytes for a batch of n problems (n = 1: a single layer on every CU)
 extern "C" size_t mi_conv3x3_wgrad_tr_batch_workspace(int n, const MiWgradDesc* descs) {
     if (!descs || n < 1 || n > MAXP) return 0;
-    long wgs[MAXP];
     for (int i = 0; i < n; ++i) if (!tr_ok(&descs[i])) return 0;
-    tr_shares(n, descs, wgs);
-    size_t fl = 0;
-    for (int i = 0; i < n; ++i) { TrArgs a; tr_plan(&descs[i], a, wgs[i]); fl += tr_ws_floats(a); }
-    return fl * sizeof(float) + 256;
+    TrArgs p[MAXP];
+    return tr_plan(n, descs, p, nullptr).ws_floats * sizeof(float) + 256;
 }
 extern "C" size_t mi_conv3x3_wgrad_tr_workspace(const MiWgradDesc* d) { return mi_conv3x3_wgrad_tr_batch_workspace(1, d); }
 
 extern "C" int mi_conv3x3_wgrad_tr_splits(const MiWgradDesc* d) {
     if (!d || !tr_ok(d)) return 0;
-    TrArgs a; tr_plan(d, a, tr_target());
+    TrArgs a; tr_geom(d, a); kslices(a, tr_target());
     return a.splits;
 }
 
@@ -606,7 +583,6 @@ extern "C" int mi_conv3x3_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, con
     MI_REQUIRE((flags & ~MI_WGRAD_STORE) == 0, "unknown flag bit");
     TrBatch b;
     b.n = n;
-    long wgs[MAXP];
     for (int i = 0; i < n; ++i) {
         MI_REQUIRE(tr_ok(&descs[i]), "descriptor not supported by the LDS-DMA weight-gradient kernel (use mi_conv3x3_wgrad_io)");
         MI_REQUIRE(descs[i].mode == descs[0].mode, "one numeric mode per batch");
@@ -614,52 +590,38 @@ extern "C" int mi_conv3x3_wgrad_tr_batch_ex(int n, const MiWgradDesc* descs, con
         MI_REQUIRE(descs[i].I1 == descs[i].Ci || (P2 && P2[i]), "two-source split without P2");
         MI_REQUIRE((((uintptr_t)P[i] | (uintptr_t)Q[i] | (uintptr_t)((P2 && P2[i]) ? P2[i] : P[i])) & 15) == 0, "operands must be 16-byte aligned");
     }
-    tr_shares(n, descs, wgs);
-    size_t off = 0, lds = 0;
-    int wg = 0, tile = 0, max_splits = 1;
+    const BatchLayout lay = tr_plan(n, descs, b.p, workspace);
+    size_t lds = 0;
     for (int i = 0; i < n; ++i) {
         TrArgs& a = b.p[i];
-        tr_plan(&descs[i], a, wgs[i]);
         a.P = (const uint16_t*)P[i]; a.P2 = (const uint16_t*)((P2 && P2[i]) ? P2[i] : P[i]); a.Q = (const uint16_t*)Q[i];
         a.dW = dW[i]; a.store = (flags & MI_WGRAD_STORE) ? 1 : 0;
         a.ldp = descs[i].ldp; a.ldp2 = (P2 && P2[i]) ? descs[i].ldp2 : descs[i].ldp; a.ldq = descs[i].ldq;
-        a.ws = (float*)workspace + off;
-        off += tr_ws_floats(a);
-        static const int xcd_env = (int)mi_knob("MI_WTR_XCD", 2);
-        a.xcd_map = 0;
-        if (xcd_env && a.gx * a.gy > 1 && wg % 8 == 0) {
-            if (a.splits % 8 == 0) a.xcd_map = 1;
-            else if (xcd_env > 1 && a.splits < 8 && 8 % a.splits == 0 && (a.gx * a.gy) % (8 / a.splits) == 0) a.xcd_map = 2;
-        }
-        a.wg0 = wg; wg += a.gx * a.gy * a.splits;
-        a.tile0 = tile; if (a.splits > 1) tile += a.gx * a.gy;
-        if (a.splits > max_splits) max_splits = a.splits;
         const size_t l = descs[i].mode == 0 ? tr32_lds(a.W) : tr_lds(a.W);
         if (l > lds) lds = l;
     }
     static const int dbg = (int)mi_knob("MI_WTR_DEBUG", 0);
     if (dbg) {
-        fprintf(stderr, "[wgrad_tr] %d layers, %d workgroups\n", n, wg);
+        fprintf(stderr, "[wgrad_tr] %d layers, %d workgroups\n", n, lay.wgs);
         for (int i = 0; i < n; ++i) {
             const TrArgs& a = b.p[i];
             fprintf(stderr, "   W%-2d Ci%-4d Cj%-4d tiles %2d x splits %3d (steps/slice %3d): %.2f GFLOP per workgroup\n", a.W, a.Ci, a.Cj, a.gx * a.gy,
                     a.splits, a.sps, 2.0 * 64 * a.sps * 64 * 128 * 9 / 1e9);
         }
     }
-    MI_REQUIRE(off == 0 || (workspace && ((uintptr_t)workspace & 15) == 0 && ws_bytes >= off * sizeof(float)),
-               "workspace too small (mi_conv3x3_wgrad_tr_batch_workspace)");
+    MI_REQUIRE(ws_ok(lay.ws_floats, workspace, ws_bytes), "workspace too small (mi_conv3x3_wgrad_tr_batch_workspace)");
     hipStream_t st = (hipStream_t)stream;
     static MiPerDevice once;
     once.run([] {
         (void)hipFuncSetAttribute((const void*)wgrad_tr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)wgrad_tr32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     if (g_wtr_phase != 2) {
-        if (descs[0].mode == 0) hipLaunchKernelGGL(wgrad_tr32_kernel, dim3((unsigned)wg), dim3(512), lds, st, b);
-        else hipLaunchKernelGGL(wgrad_tr_kernel, dim3((unsigned)wg), dim3(512), lds, st, b);
+        if (descs[0].mode == 0) hipLaunchKernelGGL(wgrad_tr32_kernel, dim3((unsigned)lay.wgs), dim3(512), lds, st, b);
+        else hipLaunchKernelGGL(wgrad_tr_kernel, dim3((unsigned)lay.wgs), dim3(512), lds, st, b);
     }
-    if (g_wtr_phase != 1 && tile > 0) {
-        if (max_splits >= 64) hipLaunchKernelGGL(wgrad_tr_reduce_kernel<8>, dim3(16, 36, tile), dim3(256), 0, st, b);
-        else hipLaunchKernelGGL(wgrad_tr_reduce_kernel<2>, dim3(4, 36, tile), dim3(256), 0, st, b);
+    if (g_wtr_phase != 1 && lay.red_tiles > 0) {
+        if (lay.max_splits >= 64) hipLaunchKernelGGL(wgrad_tr_reduce_kernel<8>, dim3(16, 36, lay.red_tiles), dim3(256), 0, st, b);
+        else hipLaunchKernelGGL(wgrad_tr_reduce_kernel<2>, dim3(4, 36, lay.red_tiles), dim3(256), 0, st, b);
     }
     MI_LAUNCH_CHECK();
     return 0;

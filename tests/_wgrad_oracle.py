@@ -3,8 +3,9 @@
 Three things live here, shared by tests/test_wgrad_tr_cpu.py and tests/test_wgrad_tr_kernels_gpu.py:
   * float64 reference weight gradients, written as explicit shifted contractions over NHWC tensors in the library's
     dW[KH][KW][Ci][Cj] layout (two sources are the channel concatenation of P and P2);
-  * a restatement of the host planners (balance_shares, the per-kind shares and k-slice plans, the workgroup -> (slice, tile) maps,
-    the workspace sizes, which reduce instantiation is launched) and of the *_supported predicates;
+  * a restatement of the host planners (tr_common.h's balance_shares, kslices and batch_layout, the per-kind work measures and xcd_map
+    rules of tr_plan / w1_plan / s2_plan, the workgroup -> (slice, tile) maps, which reduce instantiation is launched) and of the
+    *_supported predicates;
   * the case lists, and edges(): which planner / geometry edges those lists reach, by name.
 A descriptor is a plain dict with the fields of MiWgradDesc (FIELDS)."""
 import torch
@@ -167,7 +168,7 @@ def balance_shares(work, tiles, target):
 
 
 def kslices(total, ntiles, wgs):
-    """(sps, splits) of one problem that is given wgs workgroups."""
+    """tr_common.h kslices: (sps, splits) of one problem that is given wgs workgroups."""
     s = max(1, min(wgs // ntiles, total))
     sps = -(-total // s)
     return sps, -(-total // sps)
@@ -187,7 +188,7 @@ def tr_shares(descs, blocks=0):
 
 
 def _finish(layers, slot_floats, g8_from):
-    """Launch bookkeeping shared by the three batched entry points: wg0, tile0, workspace, reduce instantiation."""
+    """tr_common.h batch_layout, and what the entry points derive from it: wg0, tile0, workspace, reduce instantiation (nimax: w1_launch)."""
     wg = tile = fl = 0
     max_splits, nimax = 1, 1
     for a in layers:
@@ -205,7 +206,7 @@ def _finish(layers, slot_floats, g8_from):
 
 
 def tr_plan(descs, blocks=0):
-    """mi_conv3x3_wgrad_tr_batch's plan."""
+    """wgrad_tr.hip tr_plan: mi_conv3x3_wgrad_tr_batch's plan."""
     layers = []
     wg = 0
     for d, w in zip(descs, tr_shares(descs, blocks)):
@@ -251,7 +252,7 @@ def w1_shares(descs, q32, blocks=0):
 
 
 def w1_plan(descs, q32, blocks=0):
-    """mi_conv1x1_wgrad_tr_batch's plan (and, per tap group, mi_conv_s2_wgrad_f32's)."""
+    """wgrad1x1_tr.hip w1_plan: mi_conv1x1_wgrad_tr_batch's plan (and, per tap group, s2f_group_plan: mi_conv_s2_wgrad_f32's)."""
     layers = []
     for d, w in zip(descs, w1_shares(descs, q32, blocks)):
         nt, total = w1_tiles(d), _steps(d)
@@ -262,7 +263,8 @@ def w1_plan(descs, q32, blocks=0):
 
 
 def rank_map(wg0, W, wg):
-    """wgrad1_body / wgrad_s2_body under xcd_map: workgroup wg of a problem of W workgroups that starts at wg0 -> rank by (XCD, order on it)."""
+    """tr_common.h xcd_rank (wgrad1_body, wgrad1_f32_body, wgrad_s2_body under xcd_map): workgroup wg of a problem of W workgroups that
+    starts at wg0 -> rank by (XCD, order on it)."""
     x = (wg0 + wg) & 7
     rank = (wg - ((x - wg0) & 7)) >> 3
     for xx in range(x):
@@ -281,7 +283,7 @@ def s2_shares(descs):
 
 
 def s2_plan(descs):
-    """mi_conv_s2_wgrad_tr_batch's plan."""
+    """wgrad_s2_tr.hip s2_plan: mi_conv_s2_wgrad_tr_batch's plan."""
     layers = []
     for d, w in zip(descs, s2_shares(descs)):
         nt, total = s2_tiles(d), _steps(d)
@@ -310,7 +312,7 @@ def s2f_plan(d):
 
 
 def reduce_tails(splits, G):
-    """Per slice group of the reduce: (ran the 8-wide main loop, slices left to the tail)."""
+    """tr_common.h slice_sum, per slice group: (ran the 8-wide main loop, slices left to the tail)."""
     out = set()
     for grp in range(G):
         cnt = len(range(grp, splits, G))

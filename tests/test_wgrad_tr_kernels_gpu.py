@@ -18,8 +18,8 @@ operands, <= 3e-6 fp32 3x3, <= 2e-6 fp32 1x1 and fp32 stride 2, dbias <= 1e-5; a
 Measured on the MI355X (worst over the cases; not used as bounds): rel-L2 bf16 3x3 1.6e-7, fp32 3x3 5.0e-7, bf16 1x1 3.0e-7 (dbias
 2.4e-7), fp32 1x1 3.2e-7 (dbias 1.6e-7), bf16 stride 2 1.0e-7, fp32 stride 2 1.9e-7; the worst element sits at 0.078 of its bound.
 
-What the product library cannot reach: the MI_W* knobs (MI_WTR_BLOCKS, MI_WTR_BALANCE, MI_WTR_XCD, MI_W1_NI, MI_W1_BALANCE, MI_W1_XCD,
-MI_WS2_BLOCKS, MI_WS2_BALANCE, MI_WS2_XCD) are constants outside -DMI_EXPERIMENT builds, so the proportional (non-greedy) shares, NI = 1
+What the product library cannot reach: the MI_W* knobs (MI_WTR_BLOCKS, MI_WTR_XCD, MI_W1_NI, MI_W1_XCD, MI_WS2_BLOCKS,
+MI_WS2_XCD) are constants outside -DMI_EXPERIMENT builds, so NI = 1
 at Ci % 128 == 0, xcd_map off for a multi-tile split layer of the 1x1 / stride-2 kernels, and any stride-2 plan other than the one its
 batch composition gives have no test here.  The stride-2 bf16 kernel has no blocks hook: its k-slices are one step long unless tiles x
 steps exceed 256 workgroups, which the four sps2 / sps3 / sps4 cases arrange (2 to 4 steps per slice; longer slices need larger shapes)."""
