@@ -27,11 +27,6 @@ __device__ __forceinline__ float hsum(f32x4 v) { return v.x + v.y + v.z + v.w; }
 // Sum over the workgroup of NV values per thread; every thread gets the results.  red: NV * 8 doubles.
 // The sample statistics are accumulated in fp64: the second-order formulas subtract nearly equal sums (A below, and
 // E[x^2] - mean^2), and an fp32 accumulation of 32k terms loses exactly the digits those differences keep.
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 template <int NV> __device__ __forceinline__ void block_sums(double (&v)[NV], double* red) {
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = wave_sum_d(v[i]);

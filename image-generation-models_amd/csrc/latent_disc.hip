@@ -14,28 +14,24 @@
 // such sums, and the fp64 rate costs nothing here.  No atomics: every sum has a fixed order, two runs on the same inputs agree bit for
 // bit.  Every element of every output is stored.
 // A permutation index outside [0, N) makes its element 0 and is never used as an address.
-#include "common.h"
+// The row-tile steps up to fc2 and back down from it (staging, fc1, LayerNorm-1 both ways, both fc2 contractions, fc1^T, and the fc2 / fc1 /
+// vector branches of the parameter kernel) are csrc/latent_mlp.h, shared with csrc/latent_disc_ln.hip.  Here are the input stage, the
+// BatchNorm tail and head, the tape and the entry points.  This file keeps LayerNorm-1's statistics in fp32 (T = float in latent_mlp.h),
+// as it shipped; the other file keeps them in fp64.
+#include "latent_mlp.h"
 
 namespace {
 
-constexpr int H = 256, TPB = 256, RT = 8, LMAX = 64, LDP = H + 4, TC = 16;
+constexpr int TC = 16;
 constexpr int NMAX = MI_LATENT_DISC_NMAX;
-constexpr float SLOPE = 0.2f, EPS = 1e-5f;
 
 struct Src { const float* z; int ldz; const float* h; int ldh; const float* eps; const int64_t* perm; };
-struct Par { const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3; };
-struct Grad { float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3; };
 // tape (floats): xhat1 [N][H] | h1 [N][H] | a2 [N][H] | ln [N][2] (mean, rstd) | bn [2][H] (mean, rstd) as fp64 = 4 H floats | logit [N]
 struct Tape { float *xhat1, *h1, *a2, *ln; double* bn; float* logit; };
 // workspace of the backward (floats): da2 [N][H] | dn1 [N][H] | da1 [N][H] | cols [2][H] as fp64 = 4 H floats
 struct Ws { float *da2, *dn1, *da1; double* cols; };
 // BatchNorm runs in fp64 from the fp32 a2 in both directions (statistics, normalisation, and the backward's
 // dn - mean(dn) - xhat mean(dn xhat), which for two or three rows cancels to a few parts in 1e5 of its terms).
-
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : SLOPE * v; }
-__device__ __forceinline__ float leaky_d(float v) { return v > 0.f ? 1.f : SLOPE; }
-__device__ __forceinline__ double leaky(double v) { return v > 0.0 ? v : (double)SLOPE * v; }
-__device__ __forceinline__ double leaky_d(double v) { return v > 0.0 ? 1.0 : (double)SLOPE; }
 
 __device__ __forceinline__ float load_x(const Src& s, int N, int L, int n, int j) {
     if (s.z) return s.z[(size_t)n * s.ldz + j];
@@ -48,91 +44,24 @@ __device__ __forceinline__ float load_x(const Src& s, int N, int L, int n, int j
     return s.h[(size_t)m * s.ldh + j] + expf(s.h[(size_t)m * s.ldh + L + j]) * s.eps[(size_t)m * L + j];
 }
 
-__device__ __forceinline__ void put(float* p, double v, float scale, int accumulate) {
-    *p = (float)(accumulate ? fma((double)scale, v, (double)*p) : (double)scale * v);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// block-wide sum for 256-thread blocks in a fixed order; every thread gets the result.  red: >= 4 doubles of LDS.
-__device__ __forceinline__ double block_sum_256d(double v, double* red) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // ------------------------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(TPB) void ld_fwd_rows(int N, int L, Src s, Par p, Tape t) {
     __shared__ float xs[RT][LMAX];
     __shared__ __align__(16) float hs[RT][LDP];
     __shared__ float st[RT][2];
     const int c = threadIdx.x, r0 = blockIdx.x * RT, lane = c & 63, wv = c >> 6;
-    for (int i = c; i < RT * L; i += TPB) {
-        const int r = i / L, j = i - r * L;
-        xs[r][j] = (r0 + r < N) ? load_x(s, N, L, r0 + r, j) : 0.f;
-    }
+    stage_rows(xs, r0, N, L, [=](int n, int j) { return load_x(s, N, L, n, j); });
     __syncthreads();
     float acc[RT];
-    double a[RT];
-    {
-        const double b = p.b1[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) a[r] = b;
-        for (int j = 0; j < L; ++j) {
-            const double w = p.w1[(size_t)j * H + c];
-#pragma unroll
-            for (int r = 0; r < RT; ++r) a[r] = fma((double)xs[r][j], w, a[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < RT; ++r) acc[r] = (float)a[r];
-    }
-#pragma unroll
-    for (int r = 0; r < RT; ++r) hs[r][c] = acc[r];
+    fc_in(xs, p.w1, p.b1, L, c, acc, hs);
     __syncthreads();
-    for (int r = wv; r < RT; r += 4) {                                       // LayerNorm statistics: one wave per row, two passes
-        const float4 v = *reinterpret_cast<const float4*>(&hs[r][4 * lane]);
-        const double m = wave_sum_d(((double)v.x + v.y) + ((double)v.z + v.w)) * (1.0 / H);
-        const double a = v.x - m, b = v.y - m, d = v.z - m, e = v.w - m;
-        const double q = wave_sum_d((a * a + b * b) + (d * d + e * e)) * (1.0 / H);
-        if (lane == 0) { st[r][0] = (float)m; st[r][1] = (float)(1.0 / sqrt(q + (double)EPS)); }
-    }
+    ln_stats<float>(hs, st, lane, wv);
     __syncthreads();
-    {
-        const float g = p.g1[c], be = p.be1[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const float xh = (acc[r] - st[r][0]) * st[r][1];
-            const float hv = leaky(fmaf(g, xh, be));
-            if (r0 + r < N) {
-                t.xhat1[(size_t)(r0 + r) * H + c] = xh;
-                t.h1[(size_t)(r0 + r) * H + c] = hv;
-            }
-            hs[r][c] = hv;
-        }
-    }
+    ln_act_store<float>(acc, st, p.g1[c], p.be1[c], r0, N, c, t.xhat1, t.h1, hs);
     if (c < RT && r0 + c < N) { t.ln[2 * (r0 + c)] = st[c][0]; t.ln[2 * (r0 + c) + 1] = st[c][1]; }
     __syncthreads();
     double a2[RT];
-    {
-        const double b2 = p.b2[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) a2[r] = b2;
-    }
-    for (int k = 0; k < H; k += 4) {
-        const double w0 = p.w2[(size_t)k * H + c], w1 = p.w2[(size_t)(k + 1) * H + c];
-        const double w2 = p.w2[(size_t)(k + 2) * H + c], w3 = p.w2[(size_t)(k + 3) * H + c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const float4 hv = *reinterpret_cast<const float4*>(&hs[r][k]);
-            a2[r] = fma((double)hv.w, w3, fma((double)hv.z, w2, fma((double)hv.y, w1, fma((double)hv.x, w0, a2[r]))));
-        }
-    }
+    fc256(hs, p.w2, (double)p.b2[c], c, a2);
 #pragma unroll
     for (int r = 0; r < RT; ++r)
         if (r0 + r < N) t.a2[(size_t)(r0 + r) * H + c] = (float)a2[r];
@@ -249,117 +178,16 @@ __global__ __launch_bounds__(TPB) void ld_bwd_rows(int N, int L, int training, f
     }
     __syncthreads();
     double a0[RT];
-#pragma unroll
-    for (int r = 0; r < RT; ++r) a0[r] = 0.0;
-    for (int k = 0; k < H; k += 4) {                                         // d h1[r][c] = sum_k da2[r][k] W2[c][k]: this thread's row of [in][out]
-        const float4 wv4 = *reinterpret_cast<const float4*>(&p.w2[(size_t)c * H + k]);
-        const double w0 = wv4.x, w1 = wv4.y, w2 = wv4.z, w3 = wv4.w;
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const float4 d = *reinterpret_cast<const float4*>(&ds[r][k]);
-            a0[r] = fma((double)d.w, w3, fma((double)d.z, w2, fma((double)d.y, w1, fma((double)d.x, w0, a0[r]))));
-        }
-    }
-    float dxh[RT], xr[RT];
-    {
-        const float g1 = p.g1[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int n = r0 + r;
-            float dn = 0.f, xh = 0.f;
-            if (n < N) {
-                xh = t.xhat1[(size_t)n * H + c];
-                dn = (float)a0[r] * leaky_d(t.h1[(size_t)n * H + c]);         // sign(h1) = sign of the pre-activation
-                w.dn1[(size_t)n * H + c] = dn;
-            }
-            dxh[r] = dn * g1;
-            xr[r] = xh;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RT; ++r) { ds[r][c] = dxh[r]; xs[r][c] = xr[r]; }
-    __syncthreads();
-    for (int r = wv; r < RT; r += 4) {
-        const float4 d = *reinterpret_cast<const float4*>(&ds[r][4 * lane]);
-        const float4 x = *reinterpret_cast<const float4*>(&xs[r][4 * lane]);
-        const double s1 = wave_sum_d(((double)d.x + d.y) + ((double)d.z + d.w));
-        const double s2 = wave_sum_d(((double)d.x * x.x + (double)d.y * x.y) + ((double)d.z * x.z + (double)d.w * x.w));
-        if (lane == 0) { st[r][0] = (float)(s1 * (1.0 / H)); st[r][1] = (float)(s2 * (1.0 / H)); }
-    }
-    __syncthreads();
+    fc256_t(ds, p.w2, c, a0);
     float da1[RT];
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        const int n = r0 + r;
-        float v = 0.f;
-        if (n < N) {
-            v = t.ln[2 * n + 1] * ((dxh[r] - st[r][0]) - xr[r] * st[r][1]);
-            w.da1[(size_t)n * H + c] = v;
-        }
-        da1[r] = v;
-    }
+    ln1_backward<float>(a0, p.g1[c], t.xhat1, t.h1, t.ln + 1, 2, r0, N, c, lane, wv, ds, xs, st, w.dn1, w.da1, da1);
     if (!dz) return;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RT; ++r) ds[r][c] = da1[r];
-    __syncthreads();
-    for (int o = c; o < RT * L; o += TPB) {
-        const int r = o / L, j = o - r * L, n = r0 + r;
-        if (n >= N) continue;
-        double sum = 0.0;
-        for (int k = 0; k < H; k += 4) {
-            const float4 wv4 = *reinterpret_cast<const float4*>(&p.w1[(size_t)j * H + k]);
-            const float4 d = *reinterpret_cast<const float4*>(&ds[r][k]);
-            sum = fma((double)d.w, (double)wv4.w, fma((double)d.z, (double)wv4.z, fma((double)d.y, (double)wv4.y, fma((double)d.x, (double)wv4.x, sum))));
-        }
-        put(dz + (size_t)n * lddz + j, sum, zs, zacc);
-    }
+    input_grad(da1, ds, p.w1, L, r0, N, c, dz, lddz, zs, zacc);
 }
 
-constexpr int KT = 8, NB_W2 = H / KT;
-
-// Workgroups [0, 32): d W2[k0 .. k0+8)[c]; [32, 32 + ceil(L/8)): d W1[j0 .. j0+8)[c]; the last one: d b2, d gamma1, d beta1, d b1.
-// Thread = output column c; every sum walks the rows upward.
+// d W2, d W1 and d b2, d gamma1, d beta1, d b1: the workgroups of params_common, and no others.
 __global__ __launch_bounds__(TPB) void ld_bwd_params(int N, int L, Src s, Tape t, Ws w, Grad g, float ps, int pacc) {
-    const int c = threadIdx.x, b = blockIdx.x, nbj = (L + KT - 1) / KT;
-    double acc[KT];
-#pragma unroll
-    for (int i = 0; i < KT; ++i) acc[i] = 0.0;
-    if (b < NB_W2) {
-        const int k0 = b * KT;
-        for (int n = 0; n < N; ++n) {
-            const double d = w.da2[(size_t)n * H + c];
-            const float* hrow = t.h1 + (size_t)n * H + k0;
-#pragma unroll
-            for (int i = 0; i < KT; ++i) acc[i] = fma((double)hrow[i], d, acc[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < KT; ++i) put(g.w2 + (size_t)(k0 + i) * H + c, acc[i], ps, pacc);
-    } else if (b < NB_W2 + nbj) {
-        const int j0 = (b - NB_W2) * KT;
-        for (int n = 0; n < N; ++n) {
-            const double d = w.da1[(size_t)n * H + c];
-#pragma unroll
-            for (int i = 0; i < KT; ++i)
-                if (j0 + i < L) acc[i] = fma((double)load_x(s, N, L, n, j0 + i), d, acc[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < KT; ++i)
-            if (j0 + i < L) put(g.w1 + (size_t)(j0 + i) * H + c, acc[i], ps, pacc);
-    } else {
-        for (int n = 0; n < N; ++n) {
-            const double dn = w.dn1[(size_t)n * H + c];
-            acc[0] += w.da2[(size_t)n * H + c];
-            acc[1] = fma(dn, (double)t.xhat1[(size_t)n * H + c], acc[1]);
-            acc[2] += dn;
-            acc[3] += w.da1[(size_t)n * H + c];
-        }
-        put(g.b2 + c, acc[0], ps, pacc);
-        put(g.g1 + c, acc[1], ps, pacc);
-        put(g.be1 + c, acc[2], ps, pacc);
-        put(g.b1 + c, acc[3], ps, pacc);
-    }
+    params_common(blockIdx.x, N, L, [=](int n, int j) { return load_x(s, N, L, n, j); }, t.h1, t.xhat1, w.da2, w.dn1, w.da1, g, ps, pacc);
 }
 
 inline Tape tape_of(float* base, int N) {
@@ -370,8 +198,6 @@ inline Tape tape_of(float* base, int N) {
     t.logit = t.ln + 2 * (size_t)N + 4 * H;
     return t;
 }
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 }  // namespace
 
@@ -405,11 +231,11 @@ extern "C" int mi_latent_disc_fwd(int N, int L, int Hd, const float* z, int ldz,
     MI_REQUIRE(params && tape && out3, "bad argument");
     Src s;
     MI_REQUIRE(ld_source(N, L, z, ldz, h, ldh, eps, perm, &s) == 0, "input: either z (ldz >= L) or h + eps (ldh >= 2 L) [+ perm]");
-    for (int i = 0; i < 10; ++i) MI_REQUIRE(params[i] != nullptr, "a parameter pointer is null");
+    MI_REQUIRE(all_ten_set(params), "a parameter pointer is null");
     MI_REQUIRE(training || (running_mean && running_var), "evaluation mode needs the running statistics");
     MI_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var come together");
     MI_REQUIRE(aligned16(tape), "tape: 16-byte alignment");
-    Par p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7], params[8], params[9]};
+    const Par p = par_of(params);
     Tape t = tape_of(tape, N);
     hipLaunchKernelGGL(ld_fwd_rows, dim3((N + RT - 1) / RT), dim3(TPB), 0, ST, N, L, s, p, t);
     MI_LAUNCH_CHECK();
@@ -429,11 +255,10 @@ extern "C" int mi_latent_disc_bwd(int N, int L, int Hd, const float* z, int ldz,
     Src s;
     MI_REQUIRE(ld_source(N, L, z, ldz, h, ldh, eps, perm, &s) == 0, "input: either z (ldz >= L) or h + eps (ldh >= 2 L) [+ perm]");
     MI_REQUIRE(!dz || (!perm && lddz >= L), "dz: lddz >= L, and no input gradient through a permutation");
-    for (int i = 0; i < 10; ++i) MI_REQUIRE(params[i] != nullptr && (!grads || grads[i] != nullptr), "a parameter / gradient pointer is null");
+    MI_REQUIRE(all_ten_set(params) && (!grads || all_ten_set(grads)), "a parameter / gradient pointer is null");
     MI_REQUIRE(aligned16(tape) && aligned16(workspace) && aligned16(params[0]) && aligned16(params[4]), "tape, workspace, fc1 / fc2 weights: 16-byte alignment");
-    Par p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7], params[8], params[9]};
-    Grad g = {};
-    if (grads) g = Grad{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9]};
+    const Par p = par_of(params);
+    const Grad g = grad_of(grads);
     Tape t = tape_of(const_cast<float*>(tape), N);
     Ws w;
     const size_t nh = (size_t)N * H;

@@ -11,50 +11,25 @@
 // The batch is two segments: rows [0, N0) come from x0 with target0, rows [N0, N0 + N1) from x1 with target1 (N1 = 0 is allowed), so the
 // real and the fake half of a discriminator step are one pass.  Row n of the pass is computed by the same instruction sequence
 // whichever tile and segment it falls into: the logits of a joint pass equal those of two separate passes bit for bit.
-// Conventions of csrc/latent_disc.hip: weights input-major ([in][out]: thread = output column reads them coalesced), plain FMA, every
-// tensor fp32, every SUM (the contractions, both LayerNorm statistics, the sums over the rows) accumulated in fp64 in a fixed order and
-// rounded once, no atomics, two runs agree bit for bit, every element of every output is stored.
-#include "common.h"
+// The conventions (weights input-major, fp32 tensors, fp64 sums in a fixed order) and the row-tile steps up to fc2 and back down from it
+// (staging, fc1, LayerNorm-1 both ways, both fc2 contractions, fc1^T, and the fc2 / fc1 / vector branches of the parameter kernel) are
+// csrc/latent_mlp.h, shared with csrc/latent_disc.hip.  Here are the segments, the second LayerNorm, the head and the losses, the tape
+// and the entry points.  Both LayerNorms keep their statistics in fp64 (T = double in latent_mlp.h, which says why).
+#include "latent_mlp.h"
 
 namespace {
 
-constexpr int H = 256, TPB = 256, RT = 8, LMAX = 64, LDP = H + 4;
 constexpr int NMAX = MI_LATENT_DISC_LN_NMAX;
-constexpr float SLOPE = 0.2f, EPS = 1e-5f;
 
 // rows [0, N0) from x0 (pitch ld0), rows [N0, N0 + N1) from x1 (pitch ld1)
 struct Seg { const float* x0; int ld0; const float* x1; int ld1; int N0, N1; float t0, t1; };
-struct Par { const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3; };
-struct Grad { float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3; };
 // tape (floats), N = N0 + N1: xhat1 [N][H] | h1 [N][H] | xhat2 [N][H] | rstd1 [N] | rstd2 [N] | logit [N] | loss [N]
 struct Tape { float *xhat1, *h1, *xhat2, *rstd1, *rstd2, *logit, *loss; };
 // workspace of the backward (floats): da2 [N][H] | dn1 [N][H] | da1 [N][H] | dl [N]
 struct Ws { float *da2, *dn1, *da1, *dl; };
 
-__device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : SLOPE * v; }
-__device__ __forceinline__ float leaky_d(float v) { return v > 0.f ? 1.f : SLOPE; }
-
 __device__ __forceinline__ const float* row_of(const Seg& s, int n) {
     return n < s.N0 ? s.x0 + (size_t)n * s.ld0 : s.x1 + (size_t)(n - s.N0) * s.ld1;
-}
-
-__device__ __forceinline__ void put(float* p, double v, float scale, int accumulate) {
-    *p = (float)(accumulate ? fma((double)scale, v, (double)*p) : (double)scale * v);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// block-wide sum for 256-thread blocks in a fixed order; every thread gets the result.  red: >= 4 doubles of LDS.
-__device__ __forceinline__ double block_sum_256d(double v, double* red) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // loss of one row and its derivative by the logit.  mode 0: max(x, 0) - x t + log1p(exp(-|x|)) (finite for any finite x), d = sigmoid(x) - t;
@@ -71,44 +46,6 @@ __device__ __forceinline__ double row_dloss(int mode, double x, double t) {
     return 2.0 * (x - t);
 }
 
-// LayerNorm statistics of the RT rows in hs: one wave per row, two passes.  st[r] = (mean, rstd), kept in fp64: rounding a row's mean to
-// fp32 would shift all 256 of its elements the same way, an error the sums downstream do not average out.
-__device__ __forceinline__ void ln_stats(const float (*hs)[LDP], double (*st)[2], int lane, int wv) {
-    for (int r = wv; r < RT; r += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(&hs[r][4 * lane]);
-        const double m = wave_sum_d(((double)v.x + v.y) + ((double)v.z + v.w)) * (1.0 / H);
-        const double a = v.x - m, b = v.y - m, d = v.z - m, e = v.w - m;
-        const double q = wave_sum_d((a * a + b * b) + (d * d + e * e)) * (1.0 / H);
-        if (lane == 0) { st[r][0] = m; st[r][1] = 1.0 / sqrt(q + (double)EPS); }
-    }
-}
-
-// the two row means LayerNorm's backward needs: st[r] = (mean(d), mean(d * x)) of the RT rows in ds / xs
-__device__ __forceinline__ void ln_bwd_stats(const float (*ds)[LDP], const float (*xs)[LDP], double (*st)[2], int lane, int wv) {
-    for (int r = wv; r < RT; r += 4) {
-        const float4 d = *reinterpret_cast<const float4*>(&ds[r][4 * lane]);
-        const float4 x = *reinterpret_cast<const float4*>(&xs[r][4 * lane]);
-        const double s1 = wave_sum_d(((double)d.x + d.y) + ((double)d.z + d.w));
-        const double s2 = wave_sum_d(((double)d.x * x.x + (double)d.y * x.y) + ((double)d.z * x.z + (double)d.w * x.w));
-        if (lane == 0) { st[r][0] = s1 * (1.0 / H); st[r][1] = s2 * (1.0 / H); }
-    }
-}
-
-// acc[r] = bias[c] + sum_k hs[r][k] W[k][c] for the RT rows in hs (W input-major), k upward
-__device__ __forceinline__ void fc256(const float (*hs)[LDP], const float* __restrict__ w, double bias, int c, double* acc) {
-#pragma unroll
-    for (int r = 0; r < RT; ++r) acc[r] = bias;
-    for (int k = 0; k < H; k += 4) {
-        const double w0 = w[(size_t)k * H + c], w1 = w[(size_t)(k + 1) * H + c];
-        const double w2 = w[(size_t)(k + 2) * H + c], w3 = w[(size_t)(k + 3) * H + c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const float4 hv = *reinterpret_cast<const float4*>(&hs[r][k]);
-            acc[r] = fma((double)hv.w, w3, fma((double)hv.z, w2, fma((double)hv.y, w1, fma((double)hv.x, w0, acc[r]))));
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(TPB) void ldl_fwd_rows(int L, int mode, Seg s, Par p, Tape t) {
     __shared__ float xs[RT][LMAX];
@@ -116,41 +53,14 @@ __global__ __launch_bounds__(TPB) void ldl_fwd_rows(int L, int mode, Seg s, Par 
     __shared__ double st[RT][2];
     const int N = s.N0 + s.N1;
     const int c = threadIdx.x, r0 = blockIdx.x * RT, lane = c & 63, wv = c >> 6;
-    for (int i = c; i < RT * L; i += TPB) {
-        const int r = i / L, j = i - r * L;
-        xs[r][j] = (r0 + r < N) ? row_of(s, r0 + r)[j] : 0.f;
-    }
+    stage_rows(xs, r0, N, L, [=](int n, int j) { return row_of(s, n)[j]; });
     __syncthreads();
     float acc[RT];
-    {
-        double a[RT];
-        const double b = p.b1[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) a[r] = b;
-        for (int j = 0; j < L; ++j) {
-            const double w = p.w1[(size_t)j * H + c];
-#pragma unroll
-            for (int r = 0; r < RT; ++r) a[r] = fma((double)xs[r][j], w, a[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < RT; ++r) { acc[r] = (float)a[r]; hs[r][c] = acc[r]; }
-    }
+    fc_in(xs, p.w1, p.b1, L, c, acc, hs);
     __syncthreads();
-    ln_stats(hs, st, lane, wv);
+    ln_stats<double>(hs, st, lane, wv);
     __syncthreads();
-    {
-        const float g = p.g1[c], be = p.be1[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const float xh = (float)(((double)acc[r] - st[r][0]) * st[r][1]);
-            const float hv = leaky(fmaf(g, xh, be));
-            if (r0 + r < N) {
-                t.xhat1[(size_t)(r0 + r) * H + c] = xh;
-                t.h1[(size_t)(r0 + r) * H + c] = hv;
-            }
-            hs[r][c] = hv;
-        }
-    }
+    ln_act_store<double>(acc, st, p.g1[c], p.be1[c], r0, N, c, t.xhat1, t.h1, hs);
     if (c < RT && r0 + c < N) t.rstd1[r0 + c] = (float)st[c][1];
     __syncthreads();
     {
@@ -161,13 +71,13 @@ __global__ __launch_bounds__(TPB) void ldl_fwd_rows(int L, int mode, Seg s, Par 
         for (int r = 0; r < RT; ++r) { acc[r] = (float)a2[r]; hs[r][c] = acc[r]; }
     }
     __syncthreads();
-    ln_stats(hs, st, lane, wv);
+    ln_stats<double>(hs, st, lane, wv);
     __syncthreads();
     {
         const float g = p.g2[c], be = p.be2[c];
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
-            const float xh = (float)(((double)acc[r] - st[r][0]) * st[r][1]);
+            const float xh = ln_xhat<double>(acc[r], st[r]);
             if (r0 + r < N) t.xhat2[(size_t)(r0 + r) * H + c] = xh;
             hs[r][c] = leaky(fmaf(g, xh, be));
         }
@@ -209,7 +119,8 @@ __global__ __launch_bounds__(TPB) void ldl_fwd_reduce(int N0, int N1, Tape t, fl
 }
 
 // ------------------------------------------------------------------------------------------------------------------ backward
-// d (c0 loss0 + c1 loss1) / d logit[n] = c_seg / N_seg * row_dloss(logit[n], t_seg).  want_ws: keep what the parameter kernel reads.
+// d (c0 loss0 + c1 loss1) / d logit[n] = c_seg / N_seg * row_dloss(logit[n], t_seg).  want_ws: keep what the parameter kernel reads; without it
+// the workspace pointers in w are null.
 __global__ __launch_bounds__(TPB) void ldl_bwd_rows(int L, int mode, Seg s, float c0, float c1, Par p, Tape t, Ws w, int want_ws,
                                                     float* __restrict__ dx0, int lddx, float xsc, int xacc) {
     __shared__ __align__(16) float ds[RT][LDP];
@@ -242,145 +153,37 @@ __global__ __launch_bounds__(TPB) void ldl_bwd_rows(int L, int mode, Seg s, floa
                 d = dls[r] * w3 * leaky_d(fmaf(g2, xh, be2)) * g2;            // d xhat2
             }
             dv[r] = d; xr[r] = xh;
-            ds[r][c] = d; xs[r][c] = xh;
         }
     }
+    ln_backward<double>(dv, xr, t.rstd2, 1, r0, N, c, lane, wv, ds, xs, st, w.da2, dv);                   // d a2
+#pragma unroll
+    for (int r = 0; r < RT; ++r) ds[r][c] = dv[r];                           // the statistics pass finished reading ds before its last barrier
     __syncthreads();
-    ln_bwd_stats(ds, xs, st, lane, wv);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        const int n = r0 + r;
-        float v = 0.f;
-        if (n < N) {
-            v = (float)((double)t.rstd2[n] * (((double)dv[r] - st[r][0]) - (double)xr[r] * st[r][1]));        // d a2
-            if (want_ws) w.da2[(size_t)n * H + c] = v;
-        }
-        dv[r] = v;
-    }
-#pragma unroll
-    for (int r = 0; r < RT; ++r) ds[r][c] = dv[r];                           // the statistics pass finished reading ds before the barrier above
-    __syncthreads();
-    {
-        double a0[RT];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) a0[r] = 0.0;
-        for (int k = 0; k < H; k += 4) {                                     // d h1[r][c] = sum_k da2[r][k] W2[c][k]: this thread's row of [in][out]
-            const float4 wv4 = *reinterpret_cast<const float4*>(&p.w2[(size_t)c * H + k]);
-            const double w0 = wv4.x, w1 = wv4.y, w2 = wv4.z, w3 = wv4.w;
-#pragma unroll
-            for (int r = 0; r < RT; ++r) {
-                const float4 d = *reinterpret_cast<const float4*>(&ds[r][k]);
-                a0[r] = fma((double)d.w, w3, fma((double)d.z, w2, fma((double)d.y, w1, fma((double)d.x, w0, a0[r]))));
-            }
-        }
-        const float g1 = p.g1[c];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int n = r0 + r;
-            float dn = 0.f, xh = 0.f;
-            if (n < N) {
-                xh = t.xhat1[(size_t)n * H + c];
-                dn = (float)a0[r] * leaky_d(t.h1[(size_t)n * H + c]);         // sign(h1) = sign of the pre-activation
-                if (want_ws) w.dn1[(size_t)n * H + c] = dn;
-            }
-            dv[r] = dn * g1;
-            xr[r] = xh;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RT; ++r) { ds[r][c] = dv[r]; xs[r][c] = xr[r]; }
-    __syncthreads();
-    ln_bwd_stats(ds, xs, st, lane, wv);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        const int n = r0 + r;
-        float v = 0.f;
-        if (n < N) {
-            v = (float)((double)t.rstd1[n] * (((double)dv[r] - st[r][0]) - (double)xr[r] * st[r][1]));        // d a1
-            if (want_ws) w.da1[(size_t)n * H + c] = v;
-        }
-        dv[r] = v;
-    }
+    double a0[RT];
+    fc256_t(ds, p.w2, c, a0);
+    ln1_backward<double>(a0, p.g1[c], t.xhat1, t.h1, t.rstd1, 1, r0, N, c, lane, wv, ds, xs, st, w.dn1, w.da1, dv);
     if (!dx0 || r0 >= s.N0) return;                                          // uniform over the workgroup
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RT; ++r) ds[r][c] = dv[r];
-    __syncthreads();
-    for (int o = c; o < RT * L; o += TPB) {
-        const int r = o / L, j = o - r * L, n = r0 + r;
-        if (n >= s.N0) continue;                                             // the input gradient goes to the first segment alone
-        double sum = 0.0;
-        for (int k = 0; k < H; k += 4) {
-            const float4 wv4 = *reinterpret_cast<const float4*>(&p.w1[(size_t)j * H + k]);
-            const float4 d = *reinterpret_cast<const float4*>(&ds[r][k]);
-            sum = fma((double)d.w, (double)wv4.w, fma((double)d.z, (double)wv4.z, fma((double)d.y, (double)wv4.y, fma((double)d.x, (double)wv4.x, sum))));
-        }
-        put(dx0 + (size_t)n * lddx + j, sum, xsc, xacc);
-    }
+    input_grad(dv, ds, p.w1, L, r0, s.N0, c, dx0, lddx, xsc, xacc);          // the input gradient goes to the first segment alone
 }
 
-constexpr int KT = 8, NB_W2 = H / KT;
-
-// Workgroups [0, 32): d W2[k0 .. k0+8)[c]; [32, 32 + ceil(L/8)): d W1[j0 .. j0+8)[c]; then one for d b2, d gamma1, d beta1, d b1 and one
-// for d gamma2, d beta2, d W3, d b3.  Thread = output column c; every sum walks the rows upward.
+// The workgroups of params_common, then one for d gamma2, d beta2, d W3, d b3.
 __global__ __launch_bounds__(TPB) void ldl_bwd_params(int L, Seg s, Par p, Tape t, Ws w, Grad g, float ps, int pacc) {
-    const int N = s.N0 + s.N1;
-    const int c = threadIdx.x, b = blockIdx.x, nbj = (L + KT - 1) / KT;
-    double acc[KT];
-#pragma unroll
-    for (int i = 0; i < KT; ++i) acc[i] = 0.0;
-    if (b < NB_W2) {
-        const int k0 = b * KT;
-        for (int n = 0; n < N; ++n) {
-            const double d = w.da2[(size_t)n * H + c];
-            const float* hrow = t.h1 + (size_t)n * H + k0;
-#pragma unroll
-            for (int i = 0; i < KT; ++i) acc[i] = fma((double)hrow[i], d, acc[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < KT; ++i) put(g.w2 + (size_t)(k0 + i) * H + c, acc[i], ps, pacc);
-    } else if (b < NB_W2 + nbj) {
-        const int j0 = (b - NB_W2) * KT;
-        for (int n = 0; n < N; ++n) {
-            const double d = w.da1[(size_t)n * H + c];
-            const float* xrow = row_of(s, n);
-#pragma unroll
-            for (int i = 0; i < KT; ++i)
-                if (j0 + i < L) acc[i] = fma((double)xrow[j0 + i], d, acc[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < KT; ++i)
-            if (j0 + i < L) put(g.w1 + (size_t)(j0 + i) * H + c, acc[i], ps, pacc);
-    } else if (b == NB_W2 + nbj) {
-        for (int n = 0; n < N; ++n) {
-            const double dn = w.dn1[(size_t)n * H + c];
-            acc[0] += w.da2[(size_t)n * H + c];
-            acc[1] = fma(dn, (double)t.xhat1[(size_t)n * H + c], acc[1]);
-            acc[2] += dn;
-            acc[3] += w.da1[(size_t)n * H + c];
-        }
-        put(g.b2 + c, acc[0], ps, pacc);
-        put(g.g1 + c, acc[1], ps, pacc);
-        put(g.be1 + c, acc[2], ps, pacc);
-        put(g.b1 + c, acc[3], ps, pacc);
-    } else {
-        const float g2 = p.g2[c], be2 = p.be2[c], w3 = p.w3[c];
-        for (int n = 0; n < N; ++n) {
-            const float xh = t.xhat2[(size_t)n * H + c], pre = fmaf(g2, xh, be2), dl = w.dl[n];
-            const double dn = (double)(dl * w3 * leaky_d(pre));              // d of the second norm's output, as the row kernel forms it
-            acc[0] = fma(dn, (double)xh, acc[0]);
-            acc[1] += dn;
-            acc[2] = fma((double)dl, (double)leaky(pre), acc[2]);
-            acc[3] += dl;
-        }
-        put(g.g2 + c, acc[0], ps, pacc);
-        put(g.be2 + c, acc[1], ps, pacc);
-        put(g.w3 + c, acc[2], ps, pacc);
-        if (c == 0) put(g.b3, acc[3], ps, pacc);
+    const int N = s.N0 + s.N1, c = threadIdx.x;
+    if (params_common(blockIdx.x, N, L, [=](int n, int j) { return row_of(s, n)[j]; }, t.h1, t.xhat1, w.da2, w.dn1, w.da1, g, ps, pacc)) return;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const float g2 = p.g2[c], be2 = p.be2[c], w3 = p.w3[c];
+    for (int n = 0; n < N; ++n) {
+        const float xh = t.xhat2[(size_t)n * H + c], pre = fmaf(g2, xh, be2), dl = w.dl[n];
+        const double dn = (double)(dl * w3 * leaky_d(pre));                  // d of the second norm's output, as the row kernel forms it
+        acc[0] = fma(dn, (double)xh, acc[0]);
+        acc[1] += dn;
+        acc[2] = fma((double)dl, (double)leaky(pre), acc[2]);
+        acc[3] += dl;
     }
+    put(g.g2 + c, acc[0], ps, pacc);
+    put(g.be2 + c, acc[1], ps, pacc);
+    put(g.w3 + c, acc[2], ps, pacc);
+    if (c == 0) put(g.b3, acc[3], ps, pacc);
 }
 
 inline Tape tape_of(float* base, int N) {
@@ -390,8 +193,6 @@ inline Tape tape_of(float* base, int N) {
     t.rstd1 = base + 3 * nh; t.rstd2 = t.rstd1 + N; t.logit = t.rstd2 + N; t.loss = t.logit + N;
     return t;
 }
-
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 const char* const SHAPE_MSG = "shape not supported (H == 256, 1 <= L <= 64, N0 >= 1, N1 >= 0, N0 + N1 <= MI_LATENT_DISC_LN_NMAX)";
 
@@ -426,9 +227,9 @@ extern "C" int mi_latent_disc_ln_fwd(int N0, int N1, int L, int Hd, const float*
     MI_REQUIRE(loss_mode == 0 || loss_mode == 1, "loss_mode: 0 (vanilla) or 1 (lsgan)");
     Seg s;
     MI_REQUIRE(seg_of(N0, N1, L, x0, ld0, x1, ld1, target0, target1, &s) == 0, "input: x0 (ld0 >= L), and x1 (ld1 >= L) when N1 > 0");
-    for (int i = 0; i < 10; ++i) MI_REQUIRE(params[i] != nullptr, "a parameter pointer is null");
+    MI_REQUIRE(all_ten_set(params), "a parameter pointer is null");
     MI_REQUIRE(aligned16(tape) && aligned16(params[8]), "tape, fc3 weight: 16-byte alignment");
-    Par p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7], params[8], params[9]};
+    const Par p = par_of(params);
     const int N = N0 + N1;
     Tape t = tape_of(tape, N);
     hipLaunchKernelGGL(ldl_fwd_rows, dim3((N + RT - 1) / RT), dim3(TPB), 0, ST, L, loss_mode, s, p, t);
@@ -450,12 +251,11 @@ extern "C" int mi_latent_disc_ln_bwd(int N0, int N1, int L, int Hd, const float*
     MI_REQUIRE(!dx0 || lddx >= L, "dx0: lddx >= L");
     Seg s;
     MI_REQUIRE(seg_of(N0, N1, L, x0, ld0, x1, ld1, target0, target1, &s) == 0, "input: x0 (ld0 >= L), and x1 (ld1 >= L) when N1 > 0");
-    for (int i = 0; i < 10; ++i) MI_REQUIRE(params[i] != nullptr && (!grads || grads[i] != nullptr), "a parameter / gradient pointer is null");
+    MI_REQUIRE(all_ten_set(params) && (!grads || all_ten_set(grads)), "a parameter / gradient pointer is null");
     MI_REQUIRE(aligned16(tape) && (!workspace || aligned16(workspace)) && aligned16(params[0]) && aligned16(params[4]),
                "tape, workspace, fc1 / fc2 weights: 16-byte alignment");
-    Par p = {params[0], params[1], params[2], params[3], params[4], params[5], params[6], params[7], params[8], params[9]};
-    Grad g = {};
-    if (grads) g = Grad{grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9]};
+    const Par p = par_of(params);
+    const Grad g = grad_of(grads);
     const int N = N0 + N1;
     Tape t = tape_of(const_cast<float*>(tape), N);
     Ws w = {};

@@ -92,7 +92,7 @@ def _check_grads(got, g64, g32, scale=1.0):
 
 
 CASES = [(2, 1, "z", 1.0), (3, 10, "h", 0.0), (33, 16, "perm", 1.0), (64, 10, "z", 0.0), (130, 37, "perm", 1.0), (64, 37, "h", 1.0),
-         (130, 1, "z", 0.0), (33, 10, "perm", 0.0)]
+         (130, 1, "z", 0.0), (33, 10, "perm", 0.0), (9, 64, "h", 1.0)]
 
 
 @pytest.mark.parametrize("N,L,source,target", CASES)
