@@ -205,6 +205,7 @@ struct AdvTargets { int real[8]; };
 //   lsgan    f = (x - 1)^2 | x^2
 //   hinge    f = max(1 - x, 1) | max(1 + x, 0): the REFERENCE's formula (losses.py:17-21), not the textbook hinge max(1 - x, 0);
 //            a tie of torch.maximum's two operands sends half the gradient each way, as torch does
+//   wasserstein (mode 3)  f = -x | +x: the WGAN critic's loss (src/models/wgan.py), dlogit = -+scale / M
 __global__ __launch_bounds__(256) void adv_loss_kernel(int S, int M, int mode, AdvTargets tg, float scale, const float* __restrict__ logit,
                                                        int ld, float* __restrict__ loss, float* __restrict__ mean_logit,
                                                        float* __restrict__ dlogit, int lddl) {
@@ -224,6 +225,8 @@ __global__ __launch_bounds__(256) void adv_loss_kernel(int S, int M, int mode, A
             } else if (mode == 1) {
                 const double u = x - (real ? 1.0 : 0.0);
                 f = u * u; d = 2.0 * u;
+            } else if (mode == 3) {
+                f = real ? -x : x; d = real ? -1.0 : 1.0;
             } else if (real) {
                 f = fmax(1.0 - x, 1.0); d = x < 0 ? -1.0 : (x == 0 ? -0.5 : 0.0);
             } else {
@@ -303,7 +306,7 @@ extern "C" int mi_bn_seg_bwd(int S, int M, int C, const float* x, const float* m
 extern "C" int mi_adv_loss(int S, int M, int mode, const int* target_is_real, float scale, const float* logit, int ld, float* loss,
                            float* mean_logit, float* dlogit, int lddl, void* stream) {
     MI_REQUIRE(S >= 1 && S <= 8 && M >= 1 && (size_t)S * M < ((size_t)1 << 28), "needs 1 <= S <= 8 segments of M >= 1 logits");
-    MI_REQUIRE(mode >= 0 && mode <= 2, "mode: 0 vanilla, 1 lsgan, 2 hinge");
+    MI_REQUIRE(mode >= 0 && mode <= 3, "mode: 0 vanilla, 1 lsgan, 2 hinge, 3 wasserstein");
     MI_REQUIRE(target_is_real && logit && loss && mean_logit, "null pointer");
     MI_REQUIRE(ld >= 1 && (!dlogit || lddl >= 1), "ld, lddl: element strides >= 1");
     AdvTargets tg = {};

@@ -1817,12 +1817,26 @@ def adv_loss(logit, targets, loss_mode="vanilla", scale=1.0, want_grad=True):
     of a zero-padded [N, 1, 1, 4] buffer, what the convolutions' backward reads -- or None.  "hinge" is the reference's formula:
     max(1 - x, 1) for real targets."""
     _need_gpu(logit)
-    N = logit.shape[0]
-    if logit.numel() != N or logit.dtype != torch.float32 or N < 1:
-        raise RuntimeError("adv_loss: float32 logits [N] or [N, 1, 1, 1] are expected")
     mode = ADV_LOSSES.get(loss_mode)
     if mode is None:
         raise NotImplementedError(f"loss_mode={loss_mode!r}: 'vanilla', 'lsgan' or 'hinge'")
+    return _adv_loss(logit, targets, mode, scale, want_grad)
+
+
+_WASSERSTEIN = 3        # mi_adv_loss' mode 3; not a `loss_mode` of the GAN, so not in ADV_LOSSES
+
+
+def critic_loss(logit, targets, scale=1.0, want_grad=True):
+    """The WGAN critic's loss per segment of the logits, with `adv_loss`'s shapes and returns: a "real" segment (True) has
+    loss = -mean(logit) and dlogit = -scale / M, a "fake" one +mean(logit) and +scale / M."""
+    _need_gpu(logit)
+    return _adv_loss(logit, targets, _WASSERSTEIN, scale, want_grad)
+
+
+def _adv_loss(logit, targets, mode, scale, want_grad):
+    N = logit.shape[0]
+    if logit.numel() != N or logit.dtype != torch.float32 or N < 1:
+        raise RuntimeError("adv_loss: float32 logits [N] or [N, 1, 1, 1] are expected")
     targets = [int(bool(t)) for t in targets]
     S = len(targets)
     if S < 1 or N % S != 0:
@@ -1993,6 +2007,21 @@ def adam_tick(state):
 def adam_step_dev(p, g, m, v, state, b1, b2, eps, gscale=1.0):
     """Adam with step count / learning rate in `state` (device float[2]): graph-capturable."""
     check(load_library().mi_adam_step_dev(p.numel(), _p(p), _p(g), _p(m), _p(v), _p(state), b1, b2, eps, gscale, _stream()), "mi_adam_step_dev")
+
+
+def rmsprop_step(p, g, v, lr, alpha=0.99, eps=1e-8, gscale=1.0):
+    """torch.optim.RMSprop's default update (no momentum, not centered, no weight decay) of the flat buffer p from g, in one launch."""
+    _need_gpu(p); _dense(p, g, v)
+    if not (p.numel() == g.numel() == v.numel()):
+        raise RuntimeError("rmsprop_step: p, g and v differ in size")
+    check(load_library().mi_rmsprop_step(p.numel(), _p(p), _p(g), _p(v), lr, alpha, eps, gscale, _stream()), "mi_rmsprop_step")
+
+
+def clamp_(p, lo, hi):
+    """torch.clamp_(p, lo, hi) on a dense fp32 tensor in one launch: NaN stays NaN, -0.0 stays -0.0."""
+    _need_gpu(p); _dense(p)
+    check(load_library().mi_clamp_inplace(p.numel(), _p(p), float(lo), float(hi), _stream()), "mi_clamp_inplace")
+    return p
 
 
 def axpby(a, x, y, accumulate):

@@ -218,6 +218,8 @@ SIGNATURES = {
     "mi_bn_seg_fwd": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _I, _I, _F, _P, _P],
     "mi_bn_seg_bwd": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P],
     "mi_adv_loss": [_I, _I, _I, C.POINTER(C.c_int), _F, _P, _I, _P, _P, _P, _I, _P],
+    "mi_rmsprop_step": [_Z, _P, _P, _P, _F, _F, _F, _F, _P],
+    "mi_clamp_inplace": [_Z, _P, _F, _F, _P],
     "mi_adam_tick": [_P, _P],
     "mi_adam_step_dev": [_Z, _P, _P, _P, _P, _P, C.c_double, C.c_double, _F, _F, _P],
     "mi_relu_fwd": [_Z, _P, _P, _P],

@@ -1,6 +1,6 @@
-"""Fused Adam over the UNet's flat parameter buffer (one kernel launch per step).
+"""Fused optimizers over flat parameter buffers (one kernel launch per net and step): `FlatAdam` and `FlatRMSprop`.
 
-Update rule = torch.optim.Adam defaults (eps 1e-8, no weight decay, no amsgrad), which is
+FlatAdam's update rule = torch.optim.Adam defaults (eps 1e-8, no weight decay, no amsgrad), which is
 what the reference's configure_optimizers builds (src/models/ddpm.py:502-512)."""
 from __future__ import annotations
 
@@ -113,3 +113,71 @@ class FlatAdam(torch.optim.Optimizer):
         if self._state is not None:                          # in place for the same reason
             self._state.view(torch.int32)[0] = self._step
             self._state[1] = float(self.param_groups[0]["lr"])
+
+
+class FlatRMSprop(torch.optim.Optimizer):
+    """torch.optim.RMSprop with its defaults (no momentum, not centered, no weight decay) over flat parameter buffers: what the
+    reference's WGAN builds (src/models/wgan.py:50-55).  `net` is one module exposing flat_params / flat_grads / mark_params_dirty,
+    or a list of them (one launch each).  Eager only: the manual-optimization models that use it are not graph-captured."""
+
+    def __init__(self, net, lr=1e-2, alpha=0.99, eps=1e-8, grad_scale=1.0):
+        self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
+        self.net = self.nets[0]
+        super().__init__([p for n in self.nets for p in n.parameters()], dict(lr=lr, alpha=alpha, eps=eps))
+        self.grad_scale = grad_scale
+        self._v = None                # one square-average buffer per net
+        self._step = 0
+
+    def zero_grad(self, set_to_none: bool = False):
+        # backward overwrites the flat gradient buffer (it zeroes it itself); nothing to do.
+        pass
+
+    def _square_avg(self):
+        dev = self.nets[0].flat_params.device
+        if self._v is None:
+            self._v = [torch.zeros_like(n.flat_params) for n in self.nets]
+        elif self._v[0].device != dev:                       # the model moved (or the state was loaded on the host): follow it
+            self._v = [v.to(dev) for v in self._v]
+        return self._v
+
+    def device_step_count(self) -> int:
+        return self._step
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        grp = self.param_groups[0]
+        self._step += 1
+        for n, v in zip(self.nets, self._square_avg()):
+            K.rmsprop_step(n.flat_params, n.flat_grads, v, grp["lr"], grp["alpha"], grp["eps"], self.grad_scale)
+            n.mark_params_dirty()
+        return loss
+
+    def state_dict(self):
+        return {"step": self._step, "v": self._v, "param_groups": [
+            {k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+
+    def load_state_dict(self, sd):
+        new_v = sd.get("v")
+        if new_v is not None:
+            xs = [new_v] if torch.is_tensor(new_v) else list(new_v)
+            if len(xs) != len(self.nets):
+                raise ValueError(f"optimizer state holds {len(xs)} square-average buffers, the optimizer has {len(self.nets)} nets")
+            new_v = []
+            for t, n in zip(xs, self.nets):
+                if t.numel() != n.flat_params.numel():
+                    raise ValueError("optimizer state does not match the flat parameter buffer")
+                new_v.append(t.detach().to(device=n.flat_params.device, dtype=torch.float32).clone().contiguous())
+        self._step = int(sd["step"])
+        if new_v is not None and self._v is not None and self._v[0].device == new_v[0].device:
+            for dst, src in zip(self._v, new_v):             # in place where the buffers exist
+                dst.copy_(src)
+        elif new_v is None and self._v is not None:
+            for dst in self._v:
+                dst.zero_()
+        else:
+            self._v = new_v
+        for g, saved in zip(self.param_groups, sd.get("param_groups", [])):
+            for k, v in saved.items():
+                if k != "params":
+                    g[k] = v

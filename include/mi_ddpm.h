@@ -745,7 +745,8 @@ int mi_bn_seg_bwd(int S, int M, int C, const float* x, const float* mean, const 
  * workgroup, fp64 sums in a fixed order.  loss[S] = mean loss of the segment, mean_logit[S], dlogit[S*M] (nullable) =
  * scale * d loss_s / d logit.  mode 0 vanilla: BCE with logits, max(-+x, 0) + log1p(exp(-|x|)), finite at |x| = 200;  1 lsgan:
  * (x - t)^2, t = 1 | 0;  2 hinge AS THE REFERENCE COMPUTES IT: real max(1 - x, 1), fake max(1 + x, 0) -- the real branch is not the
- * textbook hinge max(1 - x, 0); a tie of the two operands halves the gradient, as torch.maximum does. */
+ * textbook hinge max(1 - x, 0); a tie of the two operands halves the gradient, as torch.maximum does;  3 wasserstein (the WGAN critic,
+ * wgan.py:70-90): -x for a real segment, +x for a fake one, dlogit = -+scale / M. */
 int mi_adv_loss(int S, int M, int mode, const int* target_is_real, float scale, const float* logit, int ld, float* loss,
                 float* mean_logit, float* dlogit, int lddl, void* stream);
 
@@ -781,6 +782,13 @@ int mi_p_sample_update(int B, int C, int HW, const float* x, const float* eps_ha
  * bc1 = 1-b1^step, bc2 = 1-b2^step; grad is multiplied by gscale first (DDP average). */
 int mi_adam_step(size_t n, float* p, const float* g, float* m, float* v, float lr, float b1,
                  float b2, float eps, float bc1, float bc2, float gscale, void* stream);
+/* torch.optim.RMSprop with its defaults (no momentum, not centered, no weight decay; wgan.py:50-55) over one flat buffer, one launch:
+ * gr = gscale * g;  v = alpha * v + (1 - alpha) * gr^2;  p -= lr * gr / (sqrt(v) + eps).  An element with g = 0 and v = 0 does not move
+ * (alignment padding, pad lanes).  p, g, v: 16-byte aligned. */
+int mi_rmsprop_step(size_t n, float* p, const float* g, float* v, float lr, float alpha, float eps, float gscale, void* stream);
+/* torch.clamp_(lo, hi) in place over n floats, one launch (the WGAN critic's weight clip, wgan.py:67-68).  Written with comparisons:
+ * NaN stays NaN, -0.0 stays -0.0, +-inf go to the bounds.  lo <= hi; p may be any float-aligned sub-range of a buffer. */
+int mi_clamp_inplace(size_t n, float* p, float lo, float hi, void* stream);
 /* The same update with its step count and learning rate in device memory (state[0] = steps taken, stored as the bits of a
  * uint32; state[1] = lr as float), so that a captured hipGraph of forward + backward + optimizer step replays correctly:
  * mi_adam_tick increments state[0] (call it once per optimizer step, before the update of every buffer of that step); the bias
