@@ -616,6 +616,7 @@ struct LnArgs {
     const float* x; const float* g; const float* b; float* y; const float* dy; float* dx; float* dg; float* db;
     int M, C, ldx, ldy, lddy, lddx, accumulate; float eps;
     float* part;      // backward: this workgroup's row [2 C] = (dg | db) partial sums instead of the 2 C atomics (mi_chan_layernorm_bwd_part)
+    const float* dx_in; int lddx_in;   // backward, accumulate: dx = dx_in + grad (dx_in == dx: in place; else dx_in is only read, mi_chan_layernorm_bwd_out)
 };
 constexpr int LN_MAXV = 4;
 
@@ -721,6 +722,7 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_kernel(const LnArgs a) {
         const float inv = 1.0f / (sigma + a.eps);
         const float k2 = sigma > 0.f ? inv * inv * S / (sigma * (float)a.C) : 0.f;
         float* op = a.dx + (size_t)m * a.lddx;
+        const float* ip = a.dx_in + (size_t)m * a.lddx_in;
 #pragma unroll
         for (int k = 0; k < MAXV; ++k) {
             int q = lp + LPX * k;
@@ -732,7 +734,7 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_kernel(const LnArgs a) {
                 o.w = inv * (d[k].w * gg[k].w - mh) - k2 * c[k].w;
                 if (live != 0.f) {
                     if (a.accumulate) {
-                        float4 prev = *reinterpret_cast<const float4*>(op + 4 * q);
+                        float4 prev = *reinterpret_cast<const float4*>(ip + 4 * q);
                         o.x += prev.x; o.y += prev.y; o.z += prev.z; o.w += prev.w;
                     }
                     *reinterpret_cast<float4*>(op + 4 * q) = o;
@@ -1159,7 +1161,8 @@ static int ln_fwd_go(int M, int C, const float* x, int ldx, const float* g, cons
 }
 
 static int ln_bwd_go(int M, int C, const float* x, int ldx, const float* g, float eps, const void* dyv, int lddy, float* dx, int lddx,
-                     int accumulate_dx, float* dg, float* db, int dy16, void* stream, float* part = nullptr);
+                     int accumulate_dx, float* dg, float* db, int dy16, void* stream, float* part = nullptr,
+                     const float* dx_in = nullptr, int lddx_in = 0);
 static int ln_bwd_blocks(int M, int C) {
     const bool half = C <= 128;                       // two pixels per wave
     // every workgroup ends with 2*C atomics on the same C addresses: fewer, longer-running workgroups for wide layers
@@ -1188,14 +1191,33 @@ extern "C" int mi_chan_layernorm_bwd_part(int M, int C, const float* x, int ldx,
     MI_REQUIRE(part, "null argument");
     return ln_bwd_go(M, C, x, ldx, g, eps, dy, lddy, dx, lddx, accumulate_dx, nullptr, nullptr, dy16, stream, part);
 }
+// Out of place: dx_out = dx_in + grad, dx_in read only (arithmetic and order are the accumulating in-place call's: the same bits).  The
+// LayerNorm gradient of an attention block then leaves the block's output gradient intact for the deferred to_out weight gradient
+// that still reads it.  dx_in == dx_out is the accumulating in-place call; any other overlap of the two ranges is refused.  dg / db: partial
+// rows when `part` is given (as mi_chan_layernorm_bwd_part), else atomics into dg / db (either may be null).
+extern "C" int mi_chan_layernorm_bwd_out(int M, int C, const float* x, int ldx, const float* g, float eps,
+                                         const void* dy, int lddy, const float* dx_in, int lddx_in, float* dx_out, int lddx_out,
+                                         float* dg, float* db, float* part, int dy16, void* stream) {
+    MI_REQUIRE(dx_in && dx_out, "null argument");
+    MI_REQUIRE(M > 0 && C > 0 && lddx_in >= C && lddx_out >= C && lddx_in % 4 == 0, "dx_in / dx_out pitch");
+    if (dx_in != dx_out) {
+        const uintptr_t i0 = (uintptr_t)dx_in, i1 = i0 + ((size_t)(M - 1) * lddx_in + C) * sizeof(float);
+        const uintptr_t o0 = (uintptr_t)dx_out, o1 = o0 + ((size_t)(M - 1) * lddx_out + C) * sizeof(float);
+        MI_REQUIRE(i1 <= o0 || o1 <= i0, "dx_in and dx_out overlap without being the same tensor");
+    } else {
+        MI_REQUIRE(lddx_in == lddx_out, "dx_in == dx_out with two pitches");
+    }
+    return ln_bwd_go(M, C, x, ldx, g, eps, dy, lddy, dx_out, lddx_out, 1, dg, db, dy16, stream, part, dx_in, lddx_in);
+}
 static int ln_bwd_go(int M, int C, const float* x, int ldx, const float* g, float eps, const void* dyv, int lddy, float* dx, int lddx,
-                     int accumulate_dx, float* dg, float* db, int dy16, void* stream, float* part) {
+                     int accumulate_dx, float* dg, float* db, int dy16, void* stream, float* part, const float* dx_in, int lddx_in) {
     const float* dy = (const float*)dyv;
     MI_REQUIRE(M > 0 && C > 0 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0, "C must be a multiple of 4, <= 1024");
     MI_REQUIRE(x && g && dy && dx, "null argument");
     LnArgs a{};
     a.x = x; a.g = g; a.dy = dy; a.dx = dx; a.dg = dg; a.db = db; a.M = M; a.C = C; a.ldx = ldx; a.lddy = lddy;
     a.lddx = lddx; a.accumulate = accumulate_dx; a.eps = eps; a.part = part;
+    a.dx_in = dx_in ? dx_in : dx; a.lddx_in = dx_in ? lddx_in : lddx;
     const bool half = C <= 128;                       // two pixels per wave
     const int blocks = ln_bwd_blocks(M, C);
     hipStream_t st = (hipStream_t)stream;

@@ -192,9 +192,10 @@ class _Node(nn.Module):
 # gradient bookkeeping for the tape
 # --------------------------------------------------------------------------------------------
 class _GradMap:
-    def __init__(self):
+    def __init__(self, f32=()):
         self._g: Dict[int, torch.Tensor] = {}
         self._keep: List[torch.Tensor] = []
+        self._f32 = frozenset(id(t) for t in f32)     # residual-stream tensors stored as bf16 only: their gradients are fp32
 
     def take(self, t: torch.Tensor) -> torch.Tensor:
         return self._g.pop(id(t))
@@ -212,7 +213,8 @@ class _GradMap:
         cur = self._g.get(id(t))
         if cur is not None:
             return cur, True
-        buf = torch.empty(t.shape, device=t.device, dtype=t.dtype)     # bf16 for block-internal tensors, else fp32
+        # bf16 for block-internal tensors, else fp32 (the residual stream, whatever its tensor is stored as)
+        buf = torch.empty(t.shape, device=t.device, dtype=torch.float32 if id(t) in self._f32 else t.dtype)
         self._g[id(t)] = buf; self._keep.append(t)
         return buf, False
 
@@ -288,6 +290,11 @@ class Unet(nn.Module):
         self.fuse_final = K.debug_knob("MI_DDPM_FUSE_FINAL", "1") != "0"        # inference: final_conv.0's GroupNorm + Mish inside final_conv.1's load
         # backward WRITES the conv weights' gradients (MI_WGRAD_STORE) and zero-fills only the rest of flat_grads; 0: fill everything, add
         self.grad_store = K.debug_knob("MI_DDPM_GRAD_STORE", "1") != "0"
+        # the training step's data flow, one letter per part ("" = neither):
+        #   "A": channel LayerNorm's backward writes grad[inp] out of place, so the block's output gradient stays intact for the deferred
+        #        to_out weight gradient and the 1x1 weight gradients are not flushed once per attention block (8 layers per launch)
+        #   "B": residual-stream tensors whose every training-time reader takes the bf16 copy are written as bf16 only
+        self.step_flow = K.debug_knob("MI_DDPM_STEP_FLOW", "AB")
         self.accumulate_grads = False
         self.grad_ready_hook = None        # callable(lo, hi): flat_grads[lo:hi) is final (set by the DDP reducer)
 
@@ -492,6 +499,81 @@ class Unet(nn.Module):
         b_all = flat[A.mlp_b_off:A.mlp_b_off + A.mlp_rows]
         return lin(K.mish_fwd(temb), w_all, b_all).contiguous()
 
+    def dead_twins(self, B, H, W):
+        """Training step, bf16 mode: the residual-stream tensors NO reader takes as fp32, so that their producer writes the bf16 tensor
+        alone instead of fp32 + copy (the bf16 values are the copy's, bit for bit; their gradients stay fp32).  A tensor that enters a
+        ResnetBlock qualifies when block1's conv reads bf16 (c1_16) AND the block has a res_conv that the 1x1 tile kernel takes -- an
+        identity residual, or res_conv on the generic kernel, reads the fp32 tensor, and then the twin stays.  Downsample / Upsample read
+        the copy wherever their weight gradient does.  -> {"down": [per downs level: the Downsample output], "attn_down": [per downs
+        level: the attention output], "mid2": mid_block2's output, "attn_up" / "up": [per ups level: the attention / Upsample output]}"""
+        key = (B, H, W, self.compute_mode, self.block_storage, self.step_flow, self.s2_wgrad_tr, self.dual_out, self.final_block16)
+        cache = self.__dict__.setdefault("_dead_twins_cache", {})
+        if key in cache:
+            return cache[key]
+        A, mode = self._arch, _mode_id(self.compute_mode)
+        nl = len(A.downs)
+        plan = {"down": [False] * nl, "attn_down": [False] * nl, "mid2": False, "attn_up": [False] * len(A.ups), "up": [False] * len(A.ups)}
+        cache[key] = plan
+        if not ("B" in self.step_flow and mode == K.MODE_BF16 and self.block_storage in ("bf16", "auto") and B % 8 == 0
+                and K.debug_knob("MI_DDPM_SHADOW", "1") == "1"):
+            return plan
+        auto = self.block_storage == "auto"
+
+        def block_reads16(blk, h, w, k1=None):
+            ci, co = blk["cin"], blk["cout"]
+            if not blk["res"] or co % 32 or ci % 32 or (k1 or ci) % 8 or (ci - (k1 or ci)) % 8:
+                return False
+            if not (all(K.fast3x3_supported(B, h, w, co, co)) and all(K.fast3x3_supported(B, h, w, ci, co, k1))):
+                return False
+            if auto and (K.conv3x3_uses_splitk(B, h, w, co, co) or K.conv3x3_uses_splitk(B, h, w, ci, co, k1)):
+                return False
+            return K.conv1x1_tile_supported(B, h, w, ci, co, k1)
+
+        def s2_reads16(c, k, transposed, h, w):
+            # Downsample / Upsample of an [h, w] tensor: the conv reads the copy, and so does its weight gradient when the LDS-DMA kernel
+            # takes it (the fallbacks, conv_wgrad's ring kernels, convert the fp32 tensor while they stage it)
+            big, small = ((2 * h, 2 * w), (h, w)) if transposed else ((h, w), (h // 2, w // 2))
+            return bool(self.s2_wgrad_tr and K.igemm_bf16_in_supported(c, c, k, 2, transposed, mode, (8, 8))
+                        and K.s2_wgrad_supported(B, k, c, c, transposed, big, small, mode))
+
+        def s2_writes16(c, k, transposed, h, w):      # ... and the tap-gather kernel, whose epilogue has the bf16 output, produces it
+            return bool(self.s2_wgrad_tr and K.igemm_bf16_in_supported(c, c, k, 2, transposed, mode, (8, 8))
+                        and K.conv_gt_supported(B, h, w, c, c, k, transposed))
+
+        def attn16(c, h, w):       # to_out on the tile kernel with the bf16 output in its epilogue (what `dual_out` asks for)
+            return bool(self.dual_out and c % 32 == 0 and all(K.fast1x1_supported(B, h, w, c, 3 * _HEADS * _DHEAD))
+                        and all(K.fast1x1_supported(B, h, w, _HEADS * _DHEAD, c)))
+
+        def final16(c, h, w):
+            return bool(c % 64 == 0 and self.final_block16 and all(K.fast3x3_supported(B, h, w, c, c))
+                        and not K.conv3x3_uses_splitk(B, h, w, c, c))
+
+        def up_res1(L):             # the up-path block that pops level L's skip (None: never popped), and the level it runs at
+            j = nl - 1 - L
+            return A.ups[j]["res1"] if 0 <= j < len(A.ups) else None
+
+        for L, lvl in enumerate(A.downs):
+            h, w = H >> L, W >> L
+            if lvl["down"] is None:
+                continue                                   # the last level's attention output feeds mid_block1: an identity residual
+            c = lvl["down"]["c"]
+            plan["down"][L] = s2_writes16(c, 3, False, h, w) and block_reads16(A.downs[L + 1]["res1"], h // 2, w // 2)
+            ub = up_res1(L)
+            plan["attn_down"][L] = (attn16(c, h, w) and s2_reads16(c, 3, False, h, w)
+                                    and (ub is None or block_reads16(ub, h, w, ub["cin"] - c)))
+        if A.ups:
+            plan["mid2"] = block_reads16(A.ups[0]["res1"], H >> (nl - 1), W >> (nl - 1), A.mid2["cout"])
+        for j, lvl in enumerate(A.ups):
+            L = nl - 1 - j
+            h, w = H >> L, W >> L
+            c = lvl["up"]["c"]
+            plan["attn_up"][j] = attn16(c, h, w) and s2_reads16(c, 4, True, h, w)
+            if j + 1 < len(A.ups):
+                plan["up"][j] = s2_writes16(c, 4, True, h, w) and block_reads16(A.ups[j + 1]["res1"], 2 * h, 2 * w, c)
+            else:
+                plan["up"][j] = s2_writes16(c, 4, True, h, w) and final16(c, 2 * h, 2 * w)    # the last Upsample feeds final_conv.0's conv
+        return plan
+
     def forward_nhwc(self, x, time, record=False, time_bias_table=None):
         """x: NHWC activation [B,H,W,channels] (pixel stride 4-aligned) -> NHWC eps prediction + tape.
         time_bias_table (inference only): rows of `time_bias_table(T)` replace the time MLP."""
@@ -578,7 +660,13 @@ class Unet(nn.Module):
             zpool[1] += (nsum + 3) // 4 * 4
             return sl
 
+        # training: residual-stream tensors written as bf16 ONLY (dead_twins: no reader takes fp32); backward keeps their gradients fp32
+        twins = self.dead_twins(B, H, W) if use_sh else None
+        stream16: list = []
+
         def shadow(t):
+            if t.dtype == BF:               # a residual-stream tensor without an fp32 twin: it is the copy
+                return t
             ent = sh.get(id(t))
             if ent is None:
                 ent = (t, K.to_bf16(t))
@@ -586,7 +674,7 @@ class Unet(nn.Module):
             return ent[1]
 
         def conv(inp, pre, k, stride=1, pad=0, x2=None, residual=None, transposed_conv=False, bias=True, out_dtype=torch.float32,
-                 gn_sums=None, want16=False, soft=False):
+                 gn_sums=None, want16=False, soft=False, out16=False):
             w = sv[pre + "weight"]
             kh, kw, ci, co = w.shape
             if x2 is None and residual is None and stride == 1 and not transposed_conv:
@@ -625,6 +713,12 @@ class Unet(nn.Module):
                 oh, ow = (ih + 2 * pad - kh) // stride + 1, (iw + 2 * pad - kw) // stride + 1
             if mode == K.MODE_BF16 and stride == 2 and x2 is None and inp.dtype == BF and out_dtype == torch.float32:
                 # Downsample / Upsample on the tap-gather kernel (round 4): bf16 copy of the input, fragment-order weights
+                if out16:                           # training, no fp32 reader: the bf16 output alone (the dual epilogue's copy, bit for bit)
+                    y = K.conv_gt(inp, wfq_sh[offs[pre + "weight"]:], kh=kh, kw=kw, stride=stride, pad=pad, transposed=transposed_conv, K=ci, Nc=co,
+                                  out_hw=(oh, ow), bias=sv[pre + "bias"] if bias else None, residual=residual, out_dtype=BF)
+                    if y is not None:
+                        stream16.append(y)
+                        return y
                 y = K.conv_gt(inp, wfq_sh[offs[pre + "weight"]:], kh=kh, kw=kw, stride=stride, pad=pad, transposed=transposed_conv, K=ci, Nc=co,
                               out_hw=(oh, ow), bias=sv[pre + "bias"] if bias else None, residual=residual, want16=use_sh)
                 if y is not None:
@@ -646,7 +740,7 @@ class Unet(nn.Module):
                              wb=wf_sh[offs[pre + "weight"]:] if mode == K.MODE_BF16 else None)
             return y
 
-        def resblock(blk, inp, x2=None, want_out16=False, out16_in_eval=True):
+        def resblock(blk, inp, x2=None, want_out16=False, out16_in_eval=True, out16_only=False):
             pre, co, ci = blk["pre"], blk["cout"], blk["cin"]
             # bf16 storage of c1 / h1 / c2 when every kernel touching them has a bf16 path for this shape
             lo16 = False
@@ -661,7 +755,7 @@ class Unet(nn.Module):
                     and K.small_cin_bf16_supported(3, B, inp.shape[1], inp.shape[2], ci, co, K.ld_of(inp))):
                 c1_16 = True                      # the image -> features conv: its VALU kernels write c1 / read its gradient as bf16
             inp_c, x2_c = inp, x2
-            if c1_16 and use_sh and inp.dtype == torch.float32 and inp.shape[3] % 8 == 0:
+            if c1_16 and use_sh and inp.dtype in (torch.float32, BF) and inp.shape[3] % 8 == 0:
                 inp_c, x2_c = shadow(inp), (shadow(x2) if x2 is not None else None)
             elif c1_16 and eval16 and x2 is None and id(inp) in sh:
                 inp_c = sh[id(inp)][1]            # inference: the copy the producing GroupNorm kernel wrote along (no conversion launches)
@@ -720,11 +814,19 @@ class Unet(nn.Module):
                 r = r_pre
             elif blk["res"]:
                 r = None
-                if inp_c is not inp and inp_c.dtype == BF and (x2 is None or x2_c is not None):
+                if inp_c.dtype == BF and (x2 is None or x2_c.dtype == BF):
                     r = conv(inp_c, pre + "res_conv.", 1, x2=x2_c, soft=True)
                 if r is None:
+                    if inp.dtype != torch.float32 or (x2 is not None and x2.dtype != torch.float32):
+                        raise RuntimeError("res_conv: the 1x1 tile kernel declined a block whose input has no fp32 twin (dead_twins)")
                     r = conv(inp, pre + "res_conv.", 1, x2=x2)
-            if want_out16 and (use_sh or (eval16 and out16_in_eval)) and co % 32 == 0:
+            elif inp.dtype != torch.float32:
+                raise RuntimeError("identity residual: the block's input has no fp32 twin (dead_twins)")
+            if out16_only and use_sh and co % 32 == 0:
+                # training, no fp32 reader: the bf16 output alone, the residual added before the one rounding (the dual form's copy, bit for bit)
+                out, st2 = K.gn_mish_fwd(c2, sv[pre + "block2.block.1.weight"], sv[pre + "block2.block.1.bias"], residual=r, out_dtype=BF)
+                stream16.append(out)
+            elif want_out16 and (use_sh or (eval16 and out16_in_eval)) and co % 32 == 0:
                 out, st2, out16 = K.gn_mish_fwd(c2, sv[pre + "block2.block.1.weight"], sv[pre + "block2.block.1.bias"], residual=r, want16=True)
                 sh[id(out)] = (out, out16)
             else:
@@ -733,7 +835,7 @@ class Unet(nn.Module):
                 tape.append(("res", blk, inp, x2, c1, st1, h1, c2, st2, out, inp_c, x2_c))
             return out
 
-        def attention(at, inp, feeds_s2=False):
+        def attention(at, inp, feeds_s2=False, out16_only=False):
             pre = at["pre"]
             # bf16 storage of the attention-internal tensors (LayerNorm output, qkv, attention output and their
             # gradients) when the 1x1 tile kernels take both projections; the residual stream stays fp32
@@ -767,38 +869,43 @@ class Unet(nn.Module):
             # training: the block's output is a residual-stream tensor whose bf16 copy is wanted by the skip connection's consumer,
             # Downsample / Upsample and the next Block's conv: written by to_out's epilogue instead of a conversion pass
             # (inference: only where a Downsample / Upsample reads it -- their ring kernel takes 64-channel stages of a bf16 input)
-            out = conv(ao, pre + "fn.fn.to_out.", 1, residual=inp,
-                       want16=bool((use_sh or (feeds_s2 and not record and mode == K.MODE_BF16)) and a16 and self.dual_out
-                                   and inp.shape[3] % 32 == 0))
+            if out16_only and use_sh and a16 and self.dual_out and inp.shape[3] % 32 == 0:
+                # no fp32 reader (dead_twins): to_out adds the fp32 residual and rounds once -- the bf16 tensor alone
+                out = conv(ao, pre + "fn.fn.to_out.", 1, residual=inp, out_dtype=BF)
+                stream16.append(out)
+            else:
+                out = conv(ao, pre + "fn.fn.to_out.", 1, residual=inp,
+                           want16=bool((use_sh or (feeds_s2 and not record and mode == K.MODE_BF16)) and a16 and self.dual_out
+                                       and inp.shape[3] % 32 == 0))
             if record:
                 tape.append(("attn", at, inp, ln, qkv, ctx, kstat, ao, out))
             return out
 
         skips = []
         h = x
-        for lvl in A.downs:
+        for L, lvl in enumerate(A.downs):
             h = resblock(lvl["res1"], h, want_out16=True)        # feeds res2's first conv
             assert not tb_pending, "the time-bias rows were left to a launch that did not happen"
             h = resblock(lvl["res2"], h)
-            h = attention(lvl["attn"], h, feeds_s2=lvl["down"] is not None)
+            h = attention(lvl["attn"], h, feeds_s2=lvl["down"] is not None, out16_only=bool(twins and twins["attn_down"][L]))
             skips.append(h)
             if lvl["down"] is not None:
                 inp = h
                 # training: the skip tensor's bf16 copy (its consumer in the up path wants it too) feeds Downsample and its weight gradient
                 inp_c = shadow(inp) if s2_copy(inp.shape[3], 3, False) else s2_eval_copy(inp, 3, False)
-                h = conv(inp if inp_c is None else inp_c, lvl["down"]["pre"], 3, 2, 1)
+                h = conv(inp if inp_c is None else inp_c, lvl["down"]["pre"], 3, 2, 1, out16=bool(twins and twins["down"][L]))
                 if record:
                     tape.append(("down", lvl["down"], inp, h, inp_c))
         h = resblock(A.mid1, h)
         h = attention(A.mid_attn, h)
-        h = resblock(A.mid2, h, want_out16=True, out16_in_eval=False)    # feeds the first up block's conv (with the skip: training only)
-        for lvl in A.ups:
+        h = resblock(A.mid2, h, want_out16=True, out16_in_eval=False, out16_only=bool(twins and twins["mid2"]))    # feeds the first up block's conv (with the skip: training only)
+        for j, lvl in enumerate(A.ups):
             h = resblock(lvl["res1"], h, x2=skips.pop(), want_out16=True)          # cat((x, skip)) read in place (ddpm.py:255)
             h = resblock(lvl["res2"], h)
-            h = attention(lvl["attn"], h, feeds_s2=True)
+            h = attention(lvl["attn"], h, feeds_s2=True, out16_only=bool(twins and twins["attn_up"][j]))
             inp = h
             inp_c = shadow(inp) if s2_copy(inp.shape[3], 4, True) else s2_eval_copy(inp, 4, True)
-            h = conv(inp if inp_c is None else inp_c, lvl["up"]["pre"], 4, 2, 1, transposed_conv=True)
+            h = conv(inp if inp_c is None else inp_c, lvl["up"]["pre"], 4, 2, 1, transposed_conv=True, out16=bool(twins and twins["up"][j]))
             if record:
                 tape.append(("up", lvl["up"], inp, h, inp_c))
         # final_conv.0 is a Block too (ddpm.py:232-234): its conv output is block-internal and stored like every other Block's
@@ -826,6 +933,7 @@ class Unet(nn.Module):
         eps = conv(hF, "final_conv.1.", 1)
         if record:
             tape.append(("final", h, cF, stF, hF, eps, h_c))
+            tape.append(("stream16", stream16))        # bf16-only residual-stream tensors: their gradient buffers are fp32 all the same
             tape.append(("input", x))
         return eps, tape
 
@@ -854,7 +962,7 @@ class Unet(nn.Module):
             wd_sh, wf_sh, wdq_sh, wfq_sh = self._shadows()
         else:
             wdq32_sh, wfq32_sh = self._shadows32()
-        G = _GradMap()
+        G = _GradMap(f32=next((rec[1] for rec in tape if rec[0] == "stream16"), ()))
         # data parallel (a grad-ready hook is set): the two Upsample layers come early in backward, the two Downsample layers last; with
         # all four in one launch at the very end their 8 MB of gradients would be all-reduced after backward, exposed -- two per launch
         wq = K.WgradQueue(group=int(K.debug_knob("MI_DDPM_WGRAD_GROUP", "8")),
@@ -1038,15 +1146,28 @@ class Unet(nn.Module):
             _, at, inp, ln, qkv, ctx, kstat, ao, out = rec
             pre = at["pre"]
             dout = G.take(out)
-            G.add(inp, dout)                                           # Residual: fn(x) + x  (ddpm.py:45)
+            # flow "A": grad[inp] = dout + the LayerNorm gradient goes to a buffer of its own (below) and dout stays what the deferred to_out
+            # weight gradient reads, whenever that is issued -- the queue holds dout, ao, ln and dqkv until its flush.  Data parallel (a
+            # grad-ready hook): the flush per block stays, the block's range is reported right behind it as before (bucket timing)
+            oop = "A" in self.step_flow and hook is None
+            if not oop:
+                G.add(inp, dout)                                       # Residual: fn(x) + x  (ddpm.py:45)
             conv_bwd(dout, ao, pre + "fn.fn.to_out.", 1)
             dao = G.take(ao)
             dqkv = K.linattn_bwd(qkv, ctx, kstat, dao, _HEADS)
             conv_bwd(dqkv, ln, pre + "fn.fn.to_qkv.", 1, bias=None)
             dln = G.take(ln)
-            # the LayerNorm gradient accumulates INTO dout (grad[inp] aliases it, above): the deferred to_out weight gradient
-            # that reads dout has to be issued first
-            wq.flush(kinds=(1,))
+            if oop and G._g.get(id(inp)) is None:
+                buf = torch.empty(dout.shape, device=dout.device, dtype=torch.float32)
+                K.chan_layernorm_bwd(inp, sv[pre + "fn.norm.g"], dln, buf, True, gv[pre + "fn.norm.g"], gv[pre + "fn.norm.b"], defer=wq, dx_in=dout)
+                G.add(inp, buf)
+                return
+            if oop:
+                G.add(inp, dout)                                       # grad[inp] exists already: dout is added to it, not aliased
+            else:
+                # the LayerNorm gradient accumulates INTO dout (grad[inp] aliases it, above): the deferred to_out weight gradient
+                # that reads dout has to be issued first
+                wq.flush(kinds=(1,))
             buf, acc = G.target(inp)
             K.chan_layernorm_bwd(inp, sv[pre + "fn.norm.g"], dln, buf, acc, gv[pre + "fn.norm.g"], gv[pre + "fn.norm.b"], defer=wq)
 
@@ -1062,7 +1183,7 @@ class Unet(nn.Module):
         wq.on_flush = drain if hook is not None else None
         for rec in reversed(tape):
             kind = rec[0]
-            if kind == "input":
+            if kind in ("input", "stream16"):
                 continue
             if hook is not None:
                 rng = (A.final_range if kind == "final" else A.time_range if kind == "time" else rec[1]["range"])

@@ -926,9 +926,19 @@ def s2_wgrad_supported(N, k, Ci, Cj, transposed, big, small, mode):
     return bool(USE_WGRAD_TR and load_library().mi_conv_s2_wgrad_tr_supported(C.byref(d)))
 
 
+@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+def conv_gt_supported(N, IH, IW, K, Nc, k, transposed):
+    """Does the tap-gather kernel take the Downsample (k = 3) / Upsample (k = 4, transposed) forward conv on a dense bf16 input?"""
+    OH, OW = (2 * IH, 2 * IW) if transposed else ((IH + 2 - k) // 2 + 1, (IW + 2 - k) // 2 + 1)
+    d = MiConvDesc(N=N, IH=IH, IW=IW, OH=OH, OW=OW, K=K, Nc=Nc, KH=k, KW=k, stride=2, pad=1, transposed=int(transposed), w_kn=0,
+                   mode=MODE_BF16, K1=K, ldx=K, ldx2=0, ldy=Nc, ldr=0, accumulate=0)
+    return bool(USE_CONV_GT and Nc % 8 == 0 and load_library().mi_conv_gt_supported(C.byref(d)))
+
+
 class WgradQueue:
-    """Deferred weight gradients of the Block convs (3x3) and of the 1x1 convs.  Backward pushes (X, dY, dW) here instead of
-    launching one full-chip kernel per layer; every `group` layers of a kind go out as ONE launch (mi_conv3x3_wgrad_tr_batch /
+    """Deferred weight gradients of the Block convs (3x3) and of the 1x1 convs.  The queue holds the operands it was handed until
+    their launch (items3 / items1 / items2): a caller need not keep them alive, but must not write into them before the flush.
+    Backward pushes (X, dY, dW) here instead of launching one full-chip kernel per layer; every `group` layers of a kind go out as ONE launch (mi_conv3x3_wgrad_tr_batch /
     mi_conv1x1_wgrad_tr_batch), each layer on its share of the CUs (see include/mi_ddpm.h: an eighth of the partial-tile traffic,
     an eighth of the launches).  Layers the LDS-DMA kernels cannot take run at once through conv_wgrad.  `pushed` numbers the deferred
     layers (1, 2, ...); `flushed` = the largest n such that layers 1..n have ALL been issued (the two kinds flush independently, so a
@@ -1314,13 +1324,27 @@ def ln_conv1x1(x, g, b, wq, *, Nc, eps=1e-5, bias=None, want_ln=False):
     return (y, ln) if want_ln else y
 
 
-def chan_layernorm_bwd(x, g, dy, dx, accumulate, dg, db, eps=1e-5, defer=None):
+def chan_layernorm_bwd(x, g, dy, dx, accumulate, dg, db, eps=1e-5, defer=None, dx_in=None):
     """defer (a WgradQueue): dg / db leave as one partial row per workgroup and are added by the queue's batched row sum -- the
-    2 C atomics of every workgroup on the same addresses cost ~10 us per launch."""
+    2 C atomics of every workgroup on the same addresses cost ~10 us per launch.
+    dx_in (fp32, read only): dx = dx_in + gradient, out of place (mi_chan_layernorm_bwd_out; the bits of the accumulating in-place
+    call) -- `accumulate` is then implied."""
     N, H, W, Cc = x.shape
     e0 = _probe_open()
     lib = load_library()
-    if defer is not None and dg is not None and db is not None:
+    if dx_in is not None:
+        part = rows = None
+        if defer is not None and dg is not None and db is not None:
+            rows = lib.mi_chan_layernorm_bwd_part_rows(N * H * W, Cc)
+            part = defer.rows_buffer(x.device, rows * 2 * Cc)
+        check(lib.mi_chan_layernorm_bwd_out(N * H * W, Cc, _p(x), ld_of(x), _p(g), eps, _p(dy), ld_of(dy), _p(dx_in), ld_of(dx_in),
+                                            _p(dx), ld_of(dx), None if part is not None else _p(dg), None if part is not None else _p(db),
+                                            _p(part), _b16(dy), _stream()), "mi_chan_layernorm_bwd_out")
+        if part is not None:
+            defer.push_rowsum(part, rows, Cc, 2 * Cc, dg)
+            defer.push_rowsum(part[Cc:], rows, Cc, 2 * Cc, db)
+        accumulate = True
+    elif defer is not None and dg is not None and db is not None:
         rows = lib.mi_chan_layernorm_bwd_part_rows(N * H * W, Cc)
         part = defer.rows_buffer(x.device, rows * 2 * Cc)
         check(lib.mi_chan_layernorm_bwd_part(N * H * W, Cc, _p(x), ld_of(x), _p(g), eps, _p(dy), ld_of(dy), _p(dx), ld_of(dx),
@@ -2098,6 +2122,16 @@ def fast1x1_supported(N, H, W, K, Nc):
     dw = MiWgradDesc(N=N, GH=H, GW=W, DH=H, DW=W, Ci=K, Cj=Nc, KH=1, KW=1, stride=1, pad=0, gather_i=1, mode=MODE_BF16,
                      I1=K, ldp=8, ldp2=8, ldq=8)
     return ok, bool(lib.mi_conv3x3_wgrad_supported(C.byref(dw)))
+
+
+@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+def conv1x1_tile_supported(N, H, W, K, Nc, K1=None):
+    """Does the 1x1 tile kernel take the forward conv over dense bf16 input(s) -- K1 < K: the skip concat's two sources, K1 and K - K1
+    channels (res_conv of the up path)?  conv3x3_bf16w(ksize=1) then returns a tensor."""
+    k1 = K1 or K
+    dc = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=1, KW=1, stride=1, pad=0, transposed=0, w_kn=0,
+                    mode=MODE_BF16, K1=k1, ldx=k1, ldx2=(K - k1) if k1 < K else 0, ldy=Nc, ldr=0, accumulate=0)
+    return bool(load_library().mi_conv3x3_bf16w_supported(C.byref(dc)))
 
 
 @functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step

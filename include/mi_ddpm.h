@@ -546,6 +546,12 @@ int mi_chan_layernorm_bwd_part_rows(int M, int C);
 int mi_chan_layernorm_bwd_part(int M, int C, const float* x, int ldx, const float* g, float eps,
                                const void* dy, int lddy, float* dx, int lddx, int accumulate_dx,
                                float* part, int dy16, void* stream);
+/* out of place: dx_out = dx_in + grad with dx_in read only -- bit for bit what the accumulating in-place call leaves in dx.
+ * dx_in == dx_out (same pitch) is that call; any other overlap of the two [M][C] ranges is refused before anything is
+ * written.  part != NULL: parameter gradients as partial rows (as _part); else atomics into dg / db (either may be NULL). */
+int mi_chan_layernorm_bwd_out(int M, int C, const float* x, int ldx, const float* g, float eps,
+                              const void* dy, int lddy, const float* dx_in, int lddx_in, float* dx_out, int lddx_out,
+                              float* dg, float* db, float* part, int dy16, void* stream);
 
 /* ---- LinearAttention core (ddpm.py:157-165), heads x 32 channels -------------------------
  * qkv[b][p][3*heads*32] (q | k | v, head-major inside each), out[b][p][heads*32].
