@@ -1,6 +1,6 @@
 """Models with the reference's surface.  Import them from their modules (`src.models.ddpm`, `src.models.factor_vae`, ...), as the
 configs' `_target_`s do; `src.models.FactorVAE` and `src.models.AAE` are resolved lazily (the networks import `src.models.ddpm`, so
-nothing may be imported here at package load); `src.models.GAN` likewise."""
+nothing may be imported here at package load); `src.models.GAN` and `src.models.InfoGAN` likewise."""
 
 
 def __getattr__(name):
@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "GAN":
         from .gan import GAN
         return GAN
+    if name == "InfoGAN":
+        from .info_gan import InfoGAN
+        return InfoGAN
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

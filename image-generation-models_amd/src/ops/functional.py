@@ -1876,6 +1876,151 @@ def _adv_loss(logit, targets, mode, scale, want_grad):
     return out[0], out[1], dlogit
 
 
+# --------------------------------------------------------------------------- InfoGAN heads and latent packing (info_head.hip)
+INFO_HEAD_H = 128
+
+
+def info_head_supported(S, M, E, Dd=0, V=0, Cc=0, H=INFO_HEAD_H) -> bool:
+    """Dd = V = Cc = 0 asks about the D head alone."""
+    return load_library().mi_info_head_supported(int(S), int(M), int(E), int(H), int(Dd), int(V), int(Cc)) == 1
+
+
+def info_head_shape_ok(E) -> bool:
+    """The feature widths mi_info_head_supported accepts, answered on the host (a module's constructor asks before any device exists)."""
+    return E % 4 == 0 and 4 <= E <= 4096
+
+
+def _info_rows(t, what, dtype=torch.float32):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError(f"{what}: libmi_ddpm kernels need tensors on an MI355X (HIP) device; there is no CPU fallback")
+    if t.dim() != 2 or t.dtype != dtype or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise RuntimeError(f"{what}: {dtype} rows [N, width] with unit column stride")
+    return t
+
+
+def _info_ld(t):
+    return max(t.shape[1], t.stride(0)) if t.shape[0] > 1 else t.shape[1]
+
+
+def _info_ptrs(ts):
+    """Six pointers w_d, b_d, W1, b1, W2, b2; None entries become null."""
+    assert len(ts) == 6
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("info_head: parameters / gradients are dense float32 tensors on the HIP device")
+    return (C.c_void_p * 6)(*[0 if t is None else t.data_ptr() for t in ts])
+
+
+def info_latent(dis_c_index, cont_c, z, discrete_value):
+    """The InfoGAN generator's NHWC input [N, 1, 1, latent_dim] (a view of a [N, 1, 1, ld] buffer, ld = latent_dim rounded up to 4,
+    padded lanes 0) from dis_c_index [N, Dd] (int64), cont_c [N, Cc] and z [N, Nz]: ones at column v * Dd + d for v = dis_c_index[n, d],
+    then the continuous codes, then the noise.  One launch.  An index outside [0, discrete_value) is not detected (that would need a
+    host synchronisation): the columns of that code stay 0."""
+    dis_c_index = _info_rows(dis_c_index, "dis_c_index", torch.int64)
+    cont_c, z = _info_rows(cont_c, "cont_c"), _info_rows(z, "z")
+    _need_gpu(cont_c)
+    N, Dd = dis_c_index.shape
+    Cc, Nz, V = cont_c.shape[1], z.shape[1], int(discrete_value)
+    if cont_c.shape[0] != N or z.shape[0] != N or not dis_c_index.is_contiguous():
+        raise RuntimeError(f"info_latent: dis_c_index (dense), cont_c and z with {N} rows each are expected")
+    L = Dd * V + Cc + Nz
+    ld = (L + 3) // 4 * 4
+    out = torch.empty((N, 1, 1, ld), device=cont_c.device, dtype=torch.float32)
+    check(load_library().mi_info_latent(N, Dd, V, Cc, Nz, _p(dis_c_index), _p(cont_c), _info_ld(cont_c), _p(z) if Nz else None,
+                                        _info_ld(z) if Nz else 0, _p(out), ld, _stream()), "mi_info_latent")
+    return out[..., :L]
+
+
+def _info_feature(f):
+    """f [rows, E] or the common layer's NHWC output [rows, 1, 1, E] (a view of a padded buffer: its pitch goes to the kernel)."""
+    if not (torch.is_tensor(f) and f.is_cuda):
+        raise RuntimeError("info_head: libmi_ddpm kernels need tensors on an MI355X (HIP) device; there is no CPU fallback")
+    _need_gpu(f)
+    rows, E = f.shape[0], f.shape[-1]
+    if f.dtype != torch.float32 or f.numel() != rows * E or (E > 1 and f.stride(-1) != 1):
+        raise RuntimeError("info_head: float32 features [rows, E] or [rows, 1, 1, E] with unit column stride are expected")
+    return rows, E, (max(E, f.stride(0)) if rows > 1 else E)
+
+
+def info_head_fwd(f, params, targets, scale=1.0, codes=None, lambda_I=1.0):
+    """The InfoGAN's D head, and with codes = (dis_c_index [rows, Dd] int64, cont_c [rows, Cc], discrete_value) its Q head and the
+    mutual-information loss, on the shared feature f: LeakyReLU slope 0.01 (torch's default).  params: w_d [E], b_d [1], W1 [E, 128],
+    b1 [128], W2 [128, Qd], b2 [Qd] (weights input-major; the last four may be None without codes).  targets: one bool per segment
+    (1 or 2 equal segments of the rows).  Two launches.  Returns a record: logit [rows], loss [S] (binary cross-entropy with logits,
+    per segment), mean_logit [S], dlogit = scale * d loss_s / d logit, and with codes q1 [rows, 128], q [rows, Qd] (column v * Dd + d
+    is value v of code d), I_disc, I_cont and dq = lambda_I * d (I_disc + I_cont) / dq; the scalars are device tensors."""
+    rows, E, ldf = _info_feature(f)
+    targets = [int(bool(t)) for t in targets]
+    S = len(targets)
+    if S not in (1, 2) or rows % S != 0:
+        raise RuntimeError(f"info_head_fwd: {rows} rows do not split into {S} equal segments (1 or 2)")
+    M, dev, lib = rows // S, f.device, load_library()
+    Dd = V = Cc = ldc = 0
+    idx = cont = q1 = q = dq = None
+    if codes is not None:
+        idx, cont, V = _info_rows(codes[0], "dis_c_index", torch.int64), _info_rows(codes[1], "cont_c"), int(codes[2])
+        Dd, Cc = idx.shape[1], cont.shape[1]
+        if idx.shape[0] != rows or cont.shape[0] != rows or not idx.is_contiguous():
+            raise RuntimeError(f"info_head_fwd: dis_c_index (dense) and cont_c with {rows} rows each are expected")
+        ldc = _info_ld(cont)
+    if lib.mi_info_head_supported(S, M, E, INFO_HEAD_H, Dd, V, Cc) != 1:
+        check(-1, "mi_info_head_supported")
+    if codes is not None:
+        Qd = Dd * V + Cc
+        q1 = torch.empty((rows, INFO_HEAD_H), device=dev, dtype=torch.float32)
+        q, dq = (torch.empty((rows, Qd), device=dev, dtype=torch.float32) for _ in range(2))
+    logit, dlogit = (torch.empty(rows, device=dev, dtype=torch.float32) for _ in range(2))
+    ws = torch.empty(lib.mi_info_head_workspace_doubles(rows), device=dev, dtype=torch.float64)
+    out6 = torch.empty(6, device=dev, dtype=torch.float32)
+    check(lib.mi_info_head_fwd(S, M, E, INFO_HEAD_H, _p(f), ldf, _info_ptrs(params), targets[0], targets[-1], float(scale), Dd, V, Cc,
+                               _p(idx), _p(cont), ldc, float(lambda_I), _p(logit), _p(dlogit), _p(q1), _p(q), _p(dq), _p(ws), _p(out6),
+                               _stream()), "mi_info_head_fwd")
+    return {"S": S, "M": M, "E": E, "f": f, "ldf": ldf, "logit": logit, "dlogit": dlogit, "q1": q1, "q": q, "dq": dq, "loss": out6[0:S],
+            "mean_logit": out6[2:2 + S], "I_disc": out6[4], "I_cont": out6[5], "keep": (idx, cont)}
+
+
+def info_q_fwd(f, params):
+    """The Q head's output alone, q [rows, Qd] = LeakyReLU(LeakyReLU(f) W1 + b1) W2 + b2 (slope 0.01): one launch, no D head, no loss.
+    params: W1 [E, 128], b1 [128], W2 [128, Qd], b2 [Qd], weights input-major."""
+    rows, E, ldf = _info_feature(f)
+    Qd, lib = params[2].shape[1], load_library()
+    if lib.mi_info_head_supported(1, rows, E, INFO_HEAD_H, 0, 0, 0) != 1:
+        check(-1, "mi_info_head_supported")
+    q = torch.empty((rows, Qd), device=f.device, dtype=torch.float32)
+    check(lib.mi_info_head_fwd(1, rows, E, INFO_HEAD_H, _p(f), ldf, _info_ptrs([None, None] + list(params)), 1, 1, 1.0, 0, 0, Qd, None, None, 0,
+                               0.0, None, None, None, _p(q), None, None, None, _stream()), "mi_info_head_fwd")
+    return q
+
+
+def info_head_bwd(params, rec, grads=None, want_df=True, dlogit=None, q1=None, dq=None):
+    """Backward of `info_head_fwd` from its record (dlogit / q1 / dq override the record's).  Returns df [rows, 1, 1, E], the feature
+    gradient leaky'(f) (dlogit w_d + (leaky'(q1) (dq W2^T)) W1^T) in the shape ConvEncoder.backward_nhwc takes as dout, or None.
+    grads: six tensors like params, None for what is not wanted -- the Q gradients (W1, b1, W2, b2) as a group, the D-head gradients
+    (w_d, b_d) as a group; they are stored, not accumulated.  Two launches, one without parameter gradients."""
+    S, M, E, f = rec["S"], rec["M"], rec["E"], rec["f"]
+    rows, dev = S * M, f.device
+    dlogit = rec["dlogit"] if dlogit is None else dlogit
+    q1 = rec["q1"] if q1 is None else q1
+    dq = rec["dq"] if dq is None else dq
+    Qd = 0
+    if dq is not None:
+        Qd = dq.shape[1]
+        if not (q1 is not None and q1.shape == (rows, INFO_HEAD_H) and q1.is_contiguous() and dq.shape[0] == rows and dq.is_contiguous()
+                and q1.dtype == dq.dtype == torch.float32):
+            raise RuntimeError("info_head_bwd: dense float32 q1 [rows, 128] and dq [rows, Qd] are expected")
+    if dlogit.shape != (rows,) or not dlogit.is_contiguous() or dlogit.dtype != torch.float32:
+        raise RuntimeError("info_head_bwd: dense float32 dlogit [rows] is expected")
+    if grads is None and not want_df:
+        raise RuntimeError("info_head_bwd: neither a feature gradient nor parameter gradients asked for")
+    df = torch.empty((rows, 1, 1, E), device=dev, dtype=torch.float32) if want_df else None
+    ws = None
+    if grads is not None and grads[2] is not None:
+        ws = torch.empty((rows, INFO_HEAD_H), device=dev, dtype=torch.float32)
+    check(load_library().mi_info_head_bwd(S, M, E, INFO_HEAD_H, Qd, _p(f), rec["ldf"], _info_ptrs(params), _p(dlogit), _p(q1), _p(dq), _p(df),
+                                          E, _p(ws), _info_ptrs(grads) if grads is not None else None, _stream()), "mi_info_head_bwd")
+    return df
+
+
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)
 def _dense(*ts):
     for t in ts:

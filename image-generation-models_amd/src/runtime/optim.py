@@ -10,7 +10,9 @@ from ..ops import functional as K
 
 
 class FlatAdam(torch.optim.Optimizer):
-    """`net` is one module exposing flat_params / flat_grads / mark_params_dirty, or a list of them (one launch each)."""
+    """`net` is one module exposing flat_params / flat_grads / mark_params_dirty, or a list of them (one launch each).
+    `lr` may be a sequence with one value per net: there is then one parameter group per net, each stepping with its own learning
+    rate (torch.optim.Adam with a parameter group per net).  A scalar `lr` is one group over every net."""
 
     def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, device_state=False):
         # device_state: step count and learning rate live in a 2-word device tensor (mi_adam_step_dev) -- needed when the step is
@@ -19,7 +21,16 @@ class FlatAdam(torch.optim.Optimizer):
         self._state = None            # float32[2]: word 0 = the step count as uint32 bits, word 1 = lr
         self.nets = list(net) if isinstance(net, (list, tuple)) else [net]
         self.net = self.nets[0]
-        super().__init__([p for n in self.nets for p in n.parameters()], dict(lr=lr, betas=betas, eps=eps))
+        self.per_net_lr = isinstance(lr, (list, tuple))
+        if self.per_net_lr:
+            if device_state:
+                raise NotImplementedError("device_state=True keeps ONE learning rate on the device: a learning rate per net is eager only")
+            if len(lr) != len(self.nets):
+                raise ValueError(f"lr holds {len(lr)} values, the optimizer has {len(self.nets)} nets")
+            groups = [dict(params=list(n.parameters()), lr=float(v)) for n, v in zip(self.nets, lr)]
+            super().__init__(groups, dict(lr=float(lr[0]), betas=betas, eps=eps))
+        else:
+            super().__init__([p for n in self.nets for p in n.parameters()], dict(lr=lr, betas=betas, eps=eps))
         self.grad_scale = grad_scale
         self._m = None                # one moment buffer per net (lists in both modes, so checkpoints move between them)
         self._v = None
@@ -64,7 +75,9 @@ class FlatAdam(torch.optim.Optimizer):
                 n.mark_params_dirty()
             return loss
         self._step += 1
-        for n, m, v in zip(self.nets, ms, vs):
+        for i, (n, m, v) in enumerate(zip(self.nets, ms, vs)):
+            if self.per_net_lr:
+                grp = self.param_groups[i]
             K.adam_step(n.flat_params, n.flat_grads, m, v, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], self._step,
                         self.grad_scale)
             n.mark_params_dirty()

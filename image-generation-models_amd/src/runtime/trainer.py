@@ -289,6 +289,8 @@ class Trainer:
                 optimizer.sync_lr()                            # the captured Adam reads its learning rate from device memory
             for cb in self.callbacks:
                 cb.on_train_epoch_end(self, model)
+            if hasattr(model, "on_train_epoch_end"):           # the module's own hook, after the callbacks' (Lightning's order)
+                model.on_train_epoch_end()
             if val_dataloaders is not None and (epoch + 1) % self.check_val_every_n_epoch == 0:
                 self._validate(model, val_dataloaders, device, limit=self.limit_val_batches)
                 if self.enable_checkpointing and self.is_global_zero:

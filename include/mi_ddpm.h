@@ -756,6 +756,40 @@ int mi_bn_seg_bwd(int S, int M, int C, const float* x, const float* mean, const 
 int mi_adv_loss(int S, int M, int mode, const int* target_is_real, float scale, const float* logit, int ld, float* loss,
                 float* mean_logit, float* dlogit, int lddl, void* stream);
 
+/* ---- InfoGAN heads and latent packing (reference src/models/info_gan.py:37-43, 64-133; csrc/info_head.hip) ----
+ * The heads sit on the shared feature f [S*M][E] (rows of ldf >= E floats: the common layer's NHWC output, read in place), S <= 2 segments:
+ *   a = LeakyReLU(f, 0.01) (torch's default slope; never stored), logit = a w_d + b_d, q1 = LeakyReLU(a W1 + b1, 0.01) [rows][128],
+ *   q = q1 W2 + b2 [rows][Qd], Qd = Dd V + Cc.  q's first Dd V columns are [V][Dd]: value v of code d is column v Dd + d, the layout of the
+ *   reference's flattened [N, V, Dd] one-hot; the last Cc columns are the continuous codes.
+ * params / grads: six pointers w_d [E], b_d [1], W1 [E][128], b1 [128], W2 [128][Qd], b2 [Qd] (weights input-major; W1 16-byte aligned).
+ * fp32 tensors, every sum fp64 in a fixed order and rounded once, no atomics, every element of every output stored, the workspace needs
+ * no zeroing: two runs agree bit for bit.  2 launches forward; backward 2, 1 without parameter gradients.
+ * supported: 1 for Hd == 128, E % 4 == 0, 4 <= E <= 4096, S in {1, 2}, M >= 1 and either Dd = V = Cc = 0 (the D head alone) or Dd, V,
+ *   Cc >= 1 with Dd V + Cc <= 64; else 0 with a message in mi_last_error().
+ * mi_info_latent: out [N][ld] = [ones at v Dd + d for v = dis_c_index[n][d] | cont_c [N][Cc] | z [N][Nz] | 0 up to ld], one launch, every
+ *   element written.  An index outside [0, V) is not detected (that would cost a host synchronisation): its code's V columns stay 0.
+ * fwd: the D head is computed iff logit is non-null (then params[0..1], dlogit, ws and out6 are needed; else dlogit is null too).
+ *   The Q head is computed iff q is non-null (params[2..5]); with dis_c_index [rows][Dd] also its losses (then cont_c (rows of ldc), q1,
+ *   dq, ws and out6 are needed).  With dis_c_index, cont_c and dq all null it is the Q head's output alone: q, and q1 unless null, for
+ *   Qd = Dd V + Cc in [1, 64] (Dd = V = 0, Cc = Qd will do), one launch when there is no D head either.
+ *   The adversarial loss is binary cross-entropy with logits (mi_adv_loss mode 0, the same stable form) against target{0,1}_is_real
+ *   per segment.  dlogit [rows] = scale / M * d loss_s / d logit;  dq [rows][Qd] = lambda_I * d (I_disc + I_cont) / dq with I_disc the
+ *   cross-entropy of the Dd softmaxes over V averaged over rows * Dd, I_cont the squared error averaged over rows * Cc.
+ *   ws: mi_info_head_workspace_doubles(rows) doubles.  out6 = loss of segment 0, of segment 1, mean logit of segment 0, of segment 1,
+ *   I_disc, I_cont (0 for what was not computed).
+ * bwd: from f, q1, dlogit and dq (null: the D head alone).  df (nullable, rows of lddf >= E) = leaky'(f) (dlogit w_d + (leaky'(q1) (dq W2^T)) W1^T).
+ *   grads (nullable array; each group all set or all null): [2..5] the Q gradients (need dq and dq1_ws, rows * 128 floats),
+ *   [0..1] the D-head gradients.  Gradients are stored, never accumulated. */
+int mi_info_latent(int N, int Dd, int V, int Cc, int Nz, const long long* dis_c_index, const float* cont_c, int ldc, const float* z, int ldz,
+                   float* out, int ld, void* stream);
+int mi_info_head_supported(int S, int M, int E, int Hd, int Dd, int V, int Cc);
+size_t mi_info_head_workspace_doubles(int rows);
+int mi_info_head_fwd(int S, int M, int E, int Hd, const float* f, int ldf, const float* const* params, int target0_is_real,
+                     int target1_is_real, float scale, int Dd, int V, int Cc, const long long* dis_c_index, const float* cont_c, int ldc,
+                     float lambda_I, float* logit, float* dlogit, float* q1, float* q, float* dq, double* ws, float* out6, void* stream);
+int mi_info_head_bwd(int S, int M, int E, int Hd, int Qd, const float* f, int ldf, const float* const* params, const float* dlogit,
+                     const float* q1, const float* dq, float* df, int lddf, float* dq1_ws, float* const* grads, void* stream);
+
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
 int mi_time_embed(int B, int dim, const int64_t* t, float* out, void* stream);
