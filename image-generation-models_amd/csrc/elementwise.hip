@@ -174,6 +174,22 @@ __global__ void adam_kernel(size_t n4, size_t n, float* __restrict__ p, const fl
     }
 }
 
+// adam_kernel with the complements c1 = 1 - b1 and c2 = 1 - b2 handed in, rounded once from double as torch's lerp_ / addcmul_ scalars
+// are.  adam_kernel forms them in fp32: 1.f - 0.999f is 1.0000467e-3, which scales v, and through sqrt(v / bc2) every update, by
+// 2.3e-5 against the reference -- inside the tolerances the models that use it were recorded with, so it stays as it is for them; the
+// AGE's trajectory is held to the reference's own float32 error and takes this one (FlatAdam(host_complements=True)).
+__global__ void adam_c_kernel(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                              float lr, float b2, float c1, float c2, float eps, float bc1, float bc2s, float gs) {
+    const float step = lr / bc1;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float gr = g[i] * gs;
+        const float mj = m[i] + c1 * (gr - m[i]);
+        const float vj = b2 * v[i] + c2 * gr * gr;
+        m[i] = mj; v[i] = vj;
+        p[i] -= step * mj / (sqrtf(vj) / bc2s + eps);
+    }
+}
+
 // The same update with the step count and learning rate read from device memory, so that a captured hipGraph of
 // (forward, backward, optimizer step) replays correctly: state[0] = step count (the BITS of a uint32, incremented by
 // adam_tick_kernel before the update), state[1] = learning rate (float, written by the host when a scheduler changes it).
@@ -550,6 +566,13 @@ extern "C" int mi_adam_step(size_t n, float* p, const float* g, float* m, float*
     size_t n4 = n / 4;
     hipLaunchKernelGGL(adam_kernel, dim3(nblocks(n4 ? n4 : 1, TPB, 4096)), dim3(TPB), 0, ST, n4, n, p, g, m, v, lr, b1, b2,
                        eps, bc1, sqrtf(bc2), gscale);
+    MI_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int mi_adam_step_c(size_t n, float* p, const float* g, float* m, float* v, float lr, float b2, float c1, float c2, float eps,
+                              float bc1, float bc2, float gscale, void* stream) {
+    MI_REQUIRE(n > 0 && p && g && m && v, "bad argument");
+    hipLaunchKernelGGL(adam_c_kernel, dim3(nblocks(n, TPB, 4096)), dim3(TPB), 0, ST, n, p, g, m, v, lr, b2, c1, c2, eps, bc1, sqrtf(bc2), gscale);
     MI_LAUNCH_CHECK();
     return 0;
 }

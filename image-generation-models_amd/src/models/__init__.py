@@ -1,6 +1,6 @@
 """Models with the reference's surface.  Import them from their modules (`src.models.ddpm`, `src.models.factor_vae`, ...), as the
 configs' `_target_`s do; `src.models.FactorVAE` and `src.models.AAE` are resolved lazily (the networks import `src.models.ddpm`, so
-nothing may be imported here at package load); `src.models.GAN` and `src.models.InfoGAN` likewise."""
+nothing may be imported here at package load); `src.models.GAN`, `src.models.InfoGAN` and `src.models.AGE` likewise."""
 
 
 def __getattr__(name):
@@ -16,4 +16,7 @@ def __getattr__(name):
     if name == "InfoGAN":
         from .info_gan import InfoGAN
         return InfoGAN
+    if name == "AGE":
+        from .age import AGE
+        return AGE
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

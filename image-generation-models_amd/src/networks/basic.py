@@ -113,8 +113,10 @@ class ConvDecoder(FlatNet, _NormMixin):
             tape.append(out)
         return out, tape
 
-    def backward_nhwc(self, tape, dy, need_dx=False):
-        gv = self._begin_backward()
+    def backward_nhwc(self, tape, dy, need_dx=False, param_grads=True):
+        """param_grads=False: the input gradient only -- no weight, bias or affine gradient is computed and the gradient buffer is
+        left alone (the AGE's encoder phase sends its reconstruction gradient through the frozen decoder)."""
+        gv = self._begin_backward() if param_grads else {}
         y = tape[-1]
         yb = y._base if y._base is not None else y
         d = torch.zeros_like(yb)
@@ -125,14 +127,16 @@ class ConvDecoder(FlatNet, _NormMixin):
         for i in range(3, 0, -1):
             a, st, h = tape[i]
             k, s, p = self.GEOM[i]
-            g = self._conv_bwd(g, h, f"network.{3 * i}.", k, s, p, transposed=True)
+            g = self._conv_bwd(g, h, f"network.{3 * i}.", k, s, p, transposed=True, want_dw=param_grads)
             if _is_seg(st):
                 g = self._norm_act_bwd(a, st, h, f"network.{3 * i - 2}.", "relu", 0.0, g, gv)
                 continue
+            if not param_grads:
+                raise RuntimeError("param_grads=False is built on the segmented BatchNorm path: use_fused_norm_act()")
             K.relu_bwd(h, g, out=g)
             g = self._norm_bwd(a, st, f"network.{3 * i - 2}.", g, gv)
         k, s, p = self.GEOM[0]
-        return self._conv_bwd(g, tape[0], "network.0.", k, s, p, transposed=True, want_dx=need_dx)
+        return self._conv_bwd(g, tape[0], "network.0.", k, s, p, transposed=True, want_dx=need_dx, want_dw=param_grads)
 
 
 class ConvEncoder(FlatNet, _NormMixin):

@@ -2021,6 +2021,113 @@ def info_head_bwd(params, rec, grads=None, want_df=True, dlogit=None, q1=None, d
     return df
 
 
+# --------------------------------------------------------------------------- AGE latent moments (age_ops.hip)
+AGE_RECON = {None: 0, "none": 0, "cosine": 1, "mse": 2}
+AGE_LMAX = 512
+
+
+def age_moments_supported(S, M, L) -> bool:
+    return load_library().mi_age_moments_supported(int(S), int(M), int(L)) == 1
+
+
+def _age_rows(t, what):
+    """t [rows, L] or an encoder's NHWC output [rows, 1, 1, L] (a view of a padded buffer: its pitch goes to the kernel)
+    -> (rows, L, pitch)."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError(f"{what}: libmi_ddpm kernels need tensors on an MI355X (HIP) device; there is no CPU fallback")
+    _need_gpu(t)
+    rows, L = t.shape[0], t.shape[-1]
+    if t.dtype != torch.float32 or t.dim() not in (2, 4) or t.numel() != rows * L or (L > 1 and t.stride(-1) != 1):
+        raise RuntimeError(f"{what}: float32 rows [rows, L] or [rows, 1, 1, L] with unit column stride are expected")
+    return rows, L, (max(L, t.stride(0)) if rows > 1 else L)
+
+
+def age_moments_fwd(e, segments=1, normalize=True, stats=True, recon=(None, None), target=None):
+    """The AGE's code statistics on e [S * M, L] (or the encoder's NHWC output [S * M, 1, 1, L], read in place): z = F.normalize(e) per
+    row (normalize) or z = e; per segment mu [S, L], var [S, L] (unbiased), kl = mean(mu^2 + var - log var) / 2, mean(mu), mean(var);
+    recon[s] "cosine" (1 - mean cosine similarity) or "mse" of the segment's z against target [M, L].  At most two launches.
+    Returns a record for `age_moments_bwd`; z is dense [S * M, L] with normalize, else a [S * M, L] view of e; the scalars kl [S],
+    mean_mu [S], mean_var [S], recon [S] are device tensors.  stats=False: the normalisation alone (one launch)."""
+    rows, L, ld = _age_rows(e, "age_moments_fwd: e")
+    S = int(segments)
+    modes = [AGE_RECON[m] for m in (list(recon) + [None])[:2]]
+    if S not in (1, 2) or rows % S != 0:
+        raise RuntimeError(f"age_moments_fwd: {rows} rows do not split into {S} equal segments (1 or 2)")
+    M, dev, lib = rows // S, e.device, load_library()
+    if stats and lib.mi_age_moments_supported(S, M, L) != 1:
+        check(-1, "mi_age_moments_supported")
+    ldt = 0
+    if any(modes):
+        tr, tl, ldt = _age_rows(target, "age_moments_fwd: target")
+        if (tr, tl) != (M, L):
+            raise RuntimeError(f"age_moments_fwd: target [{M}, {L}] expected, got [{tr}, {tl}]")
+    else:
+        target = None
+    z = norm = mu = var = out4 = ws = None
+    if normalize:
+        z = torch.empty((rows, L), device=dev, dtype=torch.float32)
+        norm = torch.empty(rows, device=dev, dtype=torch.float32)
+    if stats:
+        mu, var = (torch.empty((S, L), device=dev, dtype=torch.float32) for _ in range(2))
+        out4 = torch.empty((S, 4), device=dev, dtype=torch.float32)
+        if any(modes):
+            ws = torch.empty(lib.mi_age_moments_workspace_doubles(S, M), device=dev, dtype=torch.float64)
+    check(lib.mi_age_moments_fwd(S, M, L, _p(e), ld, int(bool(normalize)), _p(z), _p(norm), int(bool(stats)), modes[0], modes[1],
+                                 _p(target), ldt, _p(mu), _p(var), _p(out4), _p(ws), _stream()), "mi_age_moments_fwd")
+    rec = {"S": S, "M": M, "L": L, "e": e, "z": z if normalize else torch.as_strided(e, (rows, L), (ld, 1)), "ldz": L if normalize else ld,
+           "norm": norm, "mu": mu, "var": var, "modes": modes, "target": target, "ldt": ldt}
+    if stats:
+        rec.update(kl=out4[:, 0], mean_mu=out4[:, 1], mean_var=out4[:, 2], recon=out4[:, 3])
+    return rec
+
+
+def age_normalize(z):
+    """F.normalize(z) for rows z [N, L]: one launch."""
+    return age_moments_fwd(z, 1, normalize=True, stats=False)["z"]
+
+
+def age_moments_bwd(rec, c, w=(0.0, 0.0), dz_ext=(None, None)):
+    """Backward of `age_moments_fwd` from its record, one launch: per segment the KL coefficient c[s], the weight w[s] of the segment's
+    reconstruction term and an optional external gradient dz_ext[s] by z ([M, L] or [M, 1, 1, L], any pitch) that is added.  Returns
+    de [S * M, 1, 1, L], the gradient by e in the shape ConvEncoder.backward_nhwc takes as dout (a view of a [.., ld] buffer, ld = L
+    rounded up to 4, whose padded lanes are 0)."""
+    S, M, L = rec["S"], rec["M"], rec["L"]
+    c, w, dz_ext = (list(c) + [0.0])[:2], (list(w) + [0.0])[:2], (list(dz_ext) + [None])[:2]
+    if rec["mu"] is None:
+        raise RuntimeError("age_moments_bwd: the record holds no statistics (stats=False)")
+    ldx = 0
+    for d in dz_ext:
+        if d is not None:
+            dr, dl, pitch = _age_rows(d, "age_moments_bwd: dz_ext")
+            if (dr, dl) != (M, L) or (ldx and pitch != ldx):
+                raise RuntimeError(f"age_moments_bwd: dz_ext [{M}, {L}] with one pitch expected")
+            ldx = pitch
+    ldde = (L + 3) // 4 * 4
+    de = torch.empty((S * M, 1, 1, ldde), device=rec["z"].device, dtype=torch.float32)
+    check(load_library().mi_age_moments_bwd(S, M, L, _p(rec["z"]), rec["ldz"], _p(rec["norm"]), _p(rec["mu"]), _p(rec["var"]), float(c[0]),
+                                            float(c[1]), rec["modes"][0], rec["modes"][1], float(w[0]), float(w[1]), _p(rec["target"]),
+                                            rec["ldt"], _p(dz_ext[0]), _p(dz_ext[1]), ldx, _p(de), ldde, _stream()), "mi_age_moments_bwd")
+    return de[..., :L]
+
+
+def age_image_mse(pred_nhwc, target_nchw, want_grad=True, gscale=1.0):
+    """(F.mse_loss(pred, target), gscale * its gradient by pred) for pred NHWC [B, H, W, C] (a view of a padded buffer) and target NCHW:
+    `eps_loss(..., 1)` with the loss summed in a fixed order instead of with an atomic, so that it has the same bits on every run.
+    Two launches.  The gradient is a [B, H, W, C] view of a [.., ld] buffer whose padded lanes are 0."""
+    _need_gpu(pred_nhwc)
+    B, H, W, Cc = pred_nhwc.shape
+    if not (torch.is_tensor(target_nchw) and target_nchw.is_cuda and target_nchw.dtype == torch.float32 and target_nchw.shape == (B, Cc, H, W)):
+        raise RuntimeError(f"age_image_mse: a float32 target [{B}, {Cc}, {H}, {W}] on the HIP device is expected")
+    target_nchw = target_nchw.contiguous()
+    ld, dev, lib = ld_of(pred_nhwc), pred_nhwc.device, load_library()
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    dpred = torch.empty((B, H, W, ld), device=dev, dtype=torch.float32) if want_grad else None
+    ws = torch.empty(lib.mi_age_image_mse_workspace_doubles(B, H * W), device=dev, dtype=torch.float64)
+    check(lib.mi_age_image_mse(B, Cc, H * W, _p(pred_nhwc), ld, _p(target_nchw), _p(loss), _p(dpred), float(gscale), _p(ws), _stream()),
+          "mi_age_image_mse")
+    return loss[0], (dpred[..., :Cc] if want_grad else None)
+
+
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)
 def _dense(*ts):
     for t in ts:
@@ -2159,12 +2266,18 @@ def p_sample_update(x, eps_nhwc, z, t, tab, clip=True, want_nhwc=True, out=None,
     return xp, (xp_nhwc[..., :Cc] if want_nhwc else None)
 
 
-def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0):
+def adam_step(p, g, m, v, lr, b1, b2, eps, step, gscale=1.0, host_complements=False):
+    """host_complements: 1 - b1 and 1 - b2 are formed here in double and rounded once (mi_adam_step_c), as torch's scalars are; the
+    default forms them in fp32 on the device, where 1.f - 0.999f is off by 4.7e-5."""
     bc1 = 1.0 - b1 ** step
     bc2 = 1.0 - b2 ** step
     e0 = _probe_open()
-    check(load_library().mi_adam_step(p.numel(), _p(p), _p(g), _p(m), _p(v), lr, b1, b2, eps, bc1, bc2, gscale, _stream()),
-          "mi_adam_step")
+    if host_complements:
+        check(load_library().mi_adam_step_c(p.numel(), _p(p), _p(g), _p(m), _p(v), lr, b2, 1.0 - b1, 1.0 - b2, eps, bc1, bc2, gscale,
+                                            _stream()), "mi_adam_step_c")
+    else:
+        check(load_library().mi_adam_step(p.numel(), _p(p), _p(g), _p(m), _p(v), lr, b1, b2, eps, bc1, bc2, gscale, _stream()),
+              "mi_adam_step")
     if e0 is not None:
         _probe_close(e0, "adam_kernel", 0.0, f"{p.numel()} params", p.numel() * 28.0)
 

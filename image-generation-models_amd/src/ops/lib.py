@@ -223,6 +223,10 @@ SIGNATURES = {
     "mi_info_head_supported": [_I, _I, _I, _I, _I, _I, _I],
     "mi_info_head_fwd": [_I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _I, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P],
     "mi_info_head_bwd": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+    "mi_age_moments_supported": [_I, _I, _I],
+    "mi_age_image_mse": [_I, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P],
+    "mi_age_moments_fwd": [_I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
+    "mi_age_moments_bwd": [_I, _I, _I, _P, _I, _P, _P, _P, _F, _F, _I, _I, _F, _F, _P, _I, _P, _P, _I, _P, _I, _P],
     "mi_rmsprop_step": [_Z, _P, _P, _P, _F, _F, _F, _F, _P],
     "mi_clamp_inplace": [_Z, _P, _F, _F, _P],
     "mi_adam_tick": [_P, _P],
@@ -237,6 +241,7 @@ SIGNATURES = {
     "mi_eps_loss": [_I, _I, _I, _P, _I, _P, _I, _P, _P, _F, _P],
     "mi_p_sample_update": [_I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P],
     "mi_adam_step": [_Z, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P],
+    "mi_adam_step_c": [_Z, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _F, _F, _P],
     "mi_axpby": [_Z, _F, _P, _I, _P, _P],
     "mi_axpby2d": [_I, _I, _F, _P, _I, _I, _P, _I, _P],
     "mi_gather_rows": [_I, _I, _P, _P, _P, _P],
@@ -285,6 +290,8 @@ OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_latent_disc_ln_workspace_floats": ([_I], C.c_size_t),
          "mi_bn_seg_workspace": ([_I, _I, _I], C.c_size_t),
          "mi_info_head_workspace_doubles": ([_I], C.c_size_t),
+         "mi_age_moments_workspace_doubles": ([_I, _I], C.c_size_t),
+         "mi_age_image_mse_workspace_doubles": ([_I, _I], C.c_size_t),
          "mi_colsum_ordered_workspace": ([_I, _I], C.c_size_t),
          "mi_conv_wgrad_slabs_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),
          "mi_chan_layernorm_bwd_part_rows": ([_I, _I], C.c_int),

@@ -14,7 +14,10 @@ class FlatAdam(torch.optim.Optimizer):
     `lr` may be a sequence with one value per net: there is then one parameter group per net, each stepping with its own learning
     rate (torch.optim.Adam with a parameter group per net).  A scalar `lr` is one group over every net."""
 
-    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, device_state=False):
+    def __init__(self, net, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, device_state=False, host_complements=False):
+        # host_complements: the eager step takes 1 - beta from the host, rounded once from double (K.adam_step); the default forms them
+        # in fp32 on the device, which scales every update by 1 + 2.3e-5 at beta2 = 0.999 -- what the other models were recorded with
+        self.host_complements = bool(host_complements)
         # device_state: step count and learning rate live in a 2-word device tensor (mi_adam_step_dev) -- needed when the step is
         # captured in a hipGraph (src/runtime/graphed.py); a scheduler's new lr is copied there at the next eager call of sync_lr()
         self.device_state = device_state
@@ -64,6 +67,8 @@ class FlatAdam(torch.optim.Optimizer):
         loss = closure() if closure is not None else None
         grp = self.param_groups[0]
         ms, vs = self._moments()
+        if self.device_state and self.host_complements:
+            raise NotImplementedError("host_complements is the eager step's (mi_adam_step_c); the device-state step forms 1 - beta on the device")
         if self.device_state:
             dev = self.nets[0].flat_params.device
             if self._state is None or self._state.device != dev:
@@ -79,7 +84,7 @@ class FlatAdam(torch.optim.Optimizer):
             if self.per_net_lr:
                 grp = self.param_groups[i]
             K.adam_step(n.flat_params, n.flat_grads, m, v, grp["lr"], grp["betas"][0], grp["betas"][1], grp["eps"], self._step,
-                        self.grad_scale)
+                        self.grad_scale, host_complements=self.host_complements)
             n.mark_params_dirty()
         return loss
 

@@ -790,6 +790,39 @@ int mi_info_head_fwd(int S, int M, int E, int Hd, const float* f, int ldf, const
 int mi_info_head_bwd(int S, int M, int E, int Hd, int Qd, const float* f, int ldf, const float* const* params, const float* dlogit,
                      const float* q1, const float* dq, float* df, int lddf, float* dq1_ws, float* const* grads, void* stream);
 
+/* ---- AGE latent moments (reference src/models/age.py:64-81, 90-144; csrc/age_ops.hip) ----
+ * The code buffer e holds S <= 2 segments of M rows, L <= 512 columns, rows of ld >= L floats (the encoder's NHWC output, read in
+ * place; any pitch, no alignment assumed; columns from L on are never read).
+ * fp32 tensors, every sum fp64 in a fixed order and rounded once, no atomics, every element of every output stored, the workspace
+ * needs no zeroing: two runs agree bit for bit.
+ * supported: 1 for S in {1, 2}, M >= 2 (the unbiased variance), 1 <= L <= 512; else 0 with a message in mi_last_error().
+ * fwd: normalize != 0: z [S*M][L] (dense) = e / max(||e||_2, 1e-12) per row (F.normalize) and norm [S*M] = ||e||_2; else z = e and both
+ *   pointers are null.  want_stats != 0: per segment mu [S][L], var [S][L] (unbiased, over the segment's rows of z) and
+ *   out4 [S][4] = kl = mean_j (mu_j^2 + var_j - log var_j) / 2, mean_j mu_j, mean_j var_j, the reconstruction loss of mode_s against the
+ *   target rows t [M][L] (rows of ldt; both segments read the same M rows): mode 0 none (stored as 0), 1: 1 - mean_i cos(z_i, t_i) as
+ *   torch's cosine_similarity computes it (each row divided by its norm clamped at 1e-8), 2: mean_ij (z_ij - t_ij)^2.
+ *   ws: mi_age_moments_workspace_doubles(S, M) doubles, needed with a mode.  2 launches; 1 without normalisation and modes, and 1
+ *   with want_stats == 0 (the normalisation alone: the prior draw; then M >= 1 is accepted and mu, var, out4 are null).
+ * bwd: one launch.  z (rows of ldz) and norm as the forward stored them, or z = e and norm = null without normalisation.
+ *   g_ij = c_s / L (mu_j / M + (1 - 1 / var_j) (z_ij - mu_j) / (M - 1)) + w_s d recon_s / d z_ij + dz_ext_s[i][j]
+ *   (dz_ext_s [M][L], rows of ldx, nullable);  de = (g - z (z . g)) / norm for norm >= 1e-12 and g / 1e-12 below (clamp_min's
+ *   derivative), de = g without normalisation.  de [S*M][ldde]: every element stored, columns from L on as 0. */
+/* mi_age_image_mse: the AGE's image reconstruction term F.mse_loss(imgs, decoder(real_z)) (age.py:109, 142) with its gradient, 2 launches:
+ *   loss[0] = mean (pred - target)^2 over B C HW (stored, not accumulated), pred NHWC with pixel pitch ld, target NCHW;
+ *   dpred [B*HW][ld] (nullable) = gscale * 2 (pred - target) / (B C HW), lanes from C on stored as 0.  As mi_eps_loss with loss_type 1,
+ *   but the workgroups' fp64 sums go to ws (mi_age_image_mse_workspace_doubles(B, HW) doubles, no zeroing) and are added in a fixed
+ *   order: the loss has the same bits on every run. */
+size_t mi_age_image_mse_workspace_doubles(int B, int HW);
+int mi_age_image_mse(int B, int C, int HW, const float* pred, int ld, const float* target, float* loss, float* dpred, float gscale,
+                     double* ws, void* stream);
+int mi_age_moments_supported(int S, int M, int L);
+size_t mi_age_moments_workspace_doubles(int S, int M);
+int mi_age_moments_fwd(int S, int M, int L, const float* e, int ld, int normalize, float* z, float* norm, int want_stats, int mode0,
+                       int mode1, const float* t, int ldt, float* mu, float* var, float* out4, double* ws, void* stream);
+int mi_age_moments_bwd(int S, int M, int L, const float* z, int ldz, const float* norm, const float* mu, const float* var, float c0,
+                       float c1, int mode0, int mode1, float w0, float w1, const float* t, int ldt, const float* dz_ext0,
+                       const float* dz_ext1, int ldx, float* de, int ldde, void* stream);
+
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
 int mi_time_embed(int B, int dim, const int64_t* t, float* out, void* stream);
@@ -822,6 +855,10 @@ int mi_p_sample_update(int B, int C, int HW, const float* x, const float* eps_ha
  * bc1 = 1-b1^step, bc2 = 1-b2^step; grad is multiplied by gscale first (DDP average). */
 int mi_adam_step(size_t n, float* p, const float* g, float* m, float* v, float lr, float b1,
                  float b2, float eps, float bc1, float bc2, float gscale, void* stream);
+/* mi_adam_step with the complements c1 = 1 - b1 and c2 = 1 - b2 formed by the caller in double and rounded once, as torch's own scalars
+ * are (mi_adam_step forms them in fp32: 1.f - 0.999f is off by 4.7e-5, every update by 2.3e-5).  The AGE's optimizers use it. */
+int mi_adam_step_c(size_t n, float* p, const float* g, float* m, float* v, float lr, float b2, float c1, float c2, float eps, float bc1,
+                   float bc2, float gscale, void* stream);
 /* torch.optim.RMSprop with its defaults (no momentum, not centered, no weight decay; wgan.py:50-55) over one flat buffer, one launch:
  * gr = gscale * g;  v = alpha * v + (1 - alpha) * gr^2;  p -= lr * gr / (sqrt(v) + eps).  An element with g = 0 and v = 0 does not move
  * (alignment padding, pad lanes).  p, g, v: 16-byte aligned. */
