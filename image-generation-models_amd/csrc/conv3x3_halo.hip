@@ -987,6 +987,11 @@ static int halo_dispatch(const MiConvDesc* d, const float* x, const float* x2, c
     MI_REQUIRE(d->K1 == d->K || x2, "two-source split without x2");
     MI_REQUIRE(d->ldx % 4 == 0 && (!x2 || d->ldx2 % 4 == 0) && (((uintptr_t)x | (uintptr_t)(x2 ? x2 : x) | (uintptr_t)w_nk_bf16) & 15) == 0,
                "activations/weights must be 16-byte aligned with ld % 4 == 0");
+    // the epilogue reads bias / residual / prior content and writes y (and the bf16 copy) one channel quad per access
+    MI_REQUIRE(d->ldy % 4 == 0 && (!residual || d->ldr % 4 == 0), "ldy % 4 == 0 (and ldr % 4 == 0 with a residual)");
+    MI_REQUIRE(((uintptr_t)y & ((io & 2) ? 7 : 15)) == 0, "y must be 16-byte aligned (8-byte for a bf16 output)");
+    MI_REQUIRE((((uintptr_t)residual | (uintptr_t)bias) & 15) == 0, "residual and bias must be 16-byte aligned");
+    MI_REQUIRE(((uintptr_t)gsum & 7) == 0, "gsum must be 8-byte aligned");
     HaloArgs a;
     a.x = x; a.x2 = x2 ? x2 : x; a.w = (const uint16_t*)w_nk_bf16; a.bias = bias; a.res = residual; a.y = y;
     a.N = d->N; a.H = d->OH; a.W = d->OW; a.K = d->K; a.Nc = d->Nc; a.K1 = d->K1; a.ldx = d->ldx;
@@ -1152,6 +1157,9 @@ static int fused_go(const MiConvDesc* d, const void* x, const float* coef, const
     int BM, CK, TH;
     MI_REQUIRE(fused_plan(d, &BM, &CK, &TH), "descriptor not supported by the fused GroupNorm+Mish+Conv3x3 kernel");
     MI_REQUIRE(d->ldx % 4 == 0 && (((uintptr_t)x | (uintptr_t)w_nk_bf16 | (uintptr_t)(coef ? coef : sums)) & 7) == 0 && !d->accumulate, "alignment / accumulate");
+    MI_REQUIRE(d->ldy % 4 == 0, "ldy % 4 == 0");
+    MI_REQUIRE(((uintptr_t)y & (io == 3 ? 7 : 15)) == 0, "y must be 16-byte aligned (8-byte for a bf16 output)");
+    MI_REQUIRE(((uintptr_t)bias & 15) == 0, "bias must be 16-byte aligned");
     HaloArgs a;
     a.x = (const float*)x; a.x2 = a.x; a.w = (const uint16_t*)w_nk_bf16; a.bias = bias; a.res = nullptr; a.y = (float*)y;
     a.N = d->N; a.H = d->OH; a.W = d->OW; a.K = d->K; a.Nc = d->Nc; a.K1 = d->K; a.ldx = d->ldx; a.ldx2 = d->ldx; a.ldy = d->ldy; a.ldr = 0;

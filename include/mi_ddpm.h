@@ -101,7 +101,10 @@ int mi_conv_gt_dual(const MiConvDesc* d, const void* x, const void* w_frag, cons
  * (d->transposed = 1 selects the flipped-tap form), but activations are staged once per
  * 9 taps and weights come from a bf16 copy laid out  w[ky][kx][Nc][K]  (k contiguous), made by
  * mi_pack_weights_bf16.  Returns <0 when the descriptor is not supported
- * (check with mi_conv3x3_bf16w_supported and fall back to mi_conv_igemm). */
+ * (check with mi_conv3x3_bf16w_supported and fall back to mi_conv_igemm).
+ * Arguments of every entry point of this kernel (refused with <0 otherwise): x, x2 and w 16-byte aligned, ldx % 4 == 0 (ldx2 with
+ * x2); ldy % 4 == 0, and ldr % 4 == 0 with a residual; y 16-byte aligned (8-byte when it is written as bf16); residual and bias
+ * 16-byte aligned; gsum 8-byte aligned -- the epilogue moves one channel quad per access. */
 int mi_conv3x3_bf16w(const MiConvDesc* d, const float* x, const float* x2, const void* w_nk_bf16,
                      const float* bias, const float* residual, float* y, void* stream);
 int mi_conv3x3_bf16w_supported(const MiConvDesc* d);

@@ -1324,15 +1324,16 @@ def _pw_fwd_dgrad_case(K, cfg, out16, pw_always, pw_tile):
 
 
 @pytest.mark.parametrize("cfg", [
-    dict(N=2, H=32, Ci=128, Co=128),             # level 0: 4 rows x 32 cols per tile
-    dict(N=4, H=16, Ci=256, Co=128, split=128),  # skip concat, 8 x 16 tiles
-    dict(N=2, H=8, Ci=64, Co=192),               # 64-pixel tiles (one 8x8 image), ragged N tile
-    dict(N=16, H=8, Ci=512, Co=512),             # 128-pixel tiles = two images
-    dict(N=4, H=4, Ci=32, Co=32),                # CK=32 path, 4 images per tile
-    dict(N=40, H=32, Ci=64, Co=128),             # many tiles
-    dict(N=1, H=64, Ci=64, Co=64),               # cfg-3 level 0: 2 rows x 64 cols
-    dict(N=8, H=64, Ci=64, Co=64),               # ... 256-pixel tiles, all eight waves along M over the one 64-channel column (N64)
-    dict(N=8, H=64, Ci=128, Co=64, split=64),    # ... the up path's skip concat into 64 channels; its data gradient has 128 outputs
+    # (the tile is what mi_conv3x3_bf16w_tile answers; tests/test_halo_kernels_gpu.py asserts it per launch and reaches the 256-pixel tiles)
+    dict(N=2, H=32, Ci=128, Co=128),             # level 0: <64,64>, 2 rows x 32 cols per tile
+    dict(N=4, H=16, Ci=256, Co=128, split=128),  # skip concat: <64,64>, 4 x 16 tiles
+    dict(N=2, H=8, Ci=64, Co=192),               # <64,64>: 64-pixel tiles (one 8x8 image), ragged N tile
+    dict(N=16, H=8, Ci=512, Co=512),             # <64,64>: one 8x8 image per tile, tiles in (P, Q) = (4, 2) order over the XCDs
+    dict(N=4, H=4, Ci=32, Co=32),                # <64,32>: CK=32 path, 4 images per tile
+    dict(N=40, H=32, Ci=64, Co=128),             # <128,64> with 8 waves: 320 tiles of 4 rows, an image's tiles on one XCD
+    dict(N=1, H=64, Ci=64, Co=64),               # cfg-3 level 0: <128,32>, 2 rows x 64 cols
+    dict(N=8, H=64, Ci=64, Co=64),               # ... <128,32> again (256 tiles of 2 rows: below the 400 a 128-pixel plan asks, 64-pixel tiles do not fit W = 64)
+    dict(N=8, H=64, Ci=128, Co=64, split=64),    # ... the up path's skip concat into 64 channels, <128,32>; its data gradient has 128 outputs
 ])
 def test_conv3x3_halo_fwd_and_dgrad(K, cfg):
     """Block's 3x3 conv (ddpm.py:116) and its data gradient through the LDS halo-tile kernel."""
