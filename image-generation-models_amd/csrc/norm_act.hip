@@ -776,6 +776,146 @@ __global__ __launch_bounds__(256) void chan_ln_bwd_kernel(const LnArgs a) {
     }
 }
 
+// ---- the same backward with U pixel groups of a wave in flight.  chan_ln_bwd_kernel is latency-bound: a wave has one group's x and dy
+// (1.5 KB) and then, only after four shuffle reductions, its dx_in (1 KB) outstanding, behind `q < nq` guards and a run-time accumulate
+// branch that keep the compiler from counting the loads (rule 1).  Here C == 4 LPX NV exactly (no guard), ACC is a template
+// argument, and the raw loads of U consecutive groups of the wave's sequence stand before the first use (in the ISA every x and dy load is issued up front; hipcc
+// sinks some of the dx_in loads behind the first group's first wait, all of them ahead of the first store and behind counted vmcnt(N)).  The groups are
+// then finished in index order by the arithmetic above, rounding for rounding: every dx and every per-lane dg / db sum gets the same
+// terms in the same order, so the bits are chan_ln_bwd_kernel's.  What is left when fewer than U groups of the wave start below M goes
+// through the same body one group at a time; no dead group is ever executed.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <bool DY16> struct LnDyRaw { typedef f32x4 type; };
+template <> struct LnDyRaw<true> { typedef u32x2 type; };          // 4 bf16
+
+template <bool DY16, int LPX, int NV, bool ACC> struct LnGroup {
+    typedef typename LnDyRaw<DY16>::type dy_t;
+    f32x4 x[NV], prev[NV]; dy_t dy[NV];
+    int m; float live;
+    // request the group's rows: pixel m0 + l / LPX, clamped to the last row (a dead lane's values are masked or dropped in finish())
+    __device__ __forceinline__ void load(const LnArgs& a, int m0, int l, int lp) {
+        m = min(m0 + l / LPX, a.M - 1);
+        live = m0 + l / LPX < a.M ? 1.f : 0.f;
+        const float* xp = a.x + (size_t)m * a.ldx;
+        const float* ip = a.dx_in + (size_t)m * a.lddx_in;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int q = lp + LPX * k;
+            x[k] = *reinterpret_cast<const f32x4*>(xp + 4 * q);
+            if constexpr (DY16) dy[k] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const uint16_t*>(a.dy) + (size_t)m * a.lddy + 4 * q);
+            else dy[k] = *reinterpret_cast<const f32x4*>(a.dy + (size_t)m * a.lddy + 4 * q);
+            if constexpr (ACC) prev[k] = *reinterpret_cast<const f32x4*>(ip + 4 * q);
+        }
+    }
+    // chan_ln_bwd_kernel's arithmetic with its roundings spelled out.  hipcc contracts a * b + c where it finds one, and finds other ones in
+    // this straight-line body than between that kernel's guards, so contraction is off here and the three places where the guarded
+    // kernel's code (every instantiation) has a fused multiply-add are written as one: dh - mh, inv * (...) - k2 * xc, ag += (dy xc) * inv.
+    // Its three statistics sums are plain products and additions.  The guarded kernel itself is still compiled with hipcc's default
+    // contraction, so the equality of the two kernels' bits holds for the code hipcc generates for it today: a compiler that contracts it
+    // differently breaks tests/test_ln_bwd_pipelined_gpu.py (hook on against hook off) with neither kernel wrong, and this list is then
+    // brought in line with the guarded kernel's new code.
+    __device__ __forceinline__ void finish(const LnArgs& a, int lp, const f32x4 (&gg)[NV], f32x4 (&ag)[NV], f32x4 (&ab)[NV]) {
+#pragma clang fp contract(off)
+        f32x4 c[NV], d[NV];
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            c[k] = x[k];
+            f32x4 dv;
+            if constexpr (DY16) dv = f32x4{__uint_as_float(dy[k].x << 16), __uint_as_float(dy[k].x & 0xffff0000u),
+                                           __uint_as_float(dy[k].y << 16), __uint_as_float(dy[k].y & 0xffff0000u)};
+            else dv = dy[k];
+            d[k] = f32x4{dv.x * live, dv.y * live, dv.z * live, dv.w * live};
+            s += c[k].x + c[k].y + c[k].z + c[k].w;
+        }
+        const float mean = group_sum<LPX>(s) / (float)a.C;
+        float s2 = 0.f, sh = 0.f, sS = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            c[k].x -= mean; c[k].y -= mean; c[k].z -= mean; c[k].w -= mean;
+            s2 += c[k].x * c[k].x + c[k].y * c[k].y + c[k].z * c[k].z + c[k].w * c[k].w;
+            float h0 = d[k].x * gg[k].x, h1 = d[k].y * gg[k].y, h2 = d[k].z * gg[k].z, h3 = d[k].w * gg[k].w;
+            sh += h0 + h1 + h2 + h3;
+            sS += h0 * c[k].x + h1 * c[k].y + h2 * c[k].z + h3 * c[k].w;
+        }
+        const float var = group_sum<LPX>(s2) / (float)a.C;
+        const float mh = group_sum<LPX>(sh) / (float)a.C;
+        const float S = group_sum<LPX>(sS);
+        const float sigma = sqrtf(var);
+        const float inv = 1.0f / (sigma + a.eps);
+        const float k2 = sigma > 0.f ? inv * inv * S / (sigma * (float)a.C) : 0.f;
+        float* op = a.dx + (size_t)m * a.lddx;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int q = lp + LPX * k;
+            f32x4 o;
+            o.x = __builtin_fmaf(inv, __builtin_fmaf(d[k].x, gg[k].x, -mh), -(k2 * c[k].x));
+            o.y = __builtin_fmaf(inv, __builtin_fmaf(d[k].y, gg[k].y, -mh), -(k2 * c[k].y));
+            o.z = __builtin_fmaf(inv, __builtin_fmaf(d[k].z, gg[k].z, -mh), -(k2 * c[k].z));
+            o.w = __builtin_fmaf(inv, __builtin_fmaf(d[k].w, gg[k].w, -mh), -(k2 * c[k].w));
+            if constexpr (ACC) { o.x += prev[k].x; o.y += prev[k].y; o.z += prev[k].z; o.w += prev[k].w; }
+            if (live != 0.f) *reinterpret_cast<f32x4*>(op + 4 * q) = o;
+            ag[k].x = __builtin_fmaf(d[k].x * c[k].x, inv, ag[k].x); ag[k].y = __builtin_fmaf(d[k].y * c[k].y, inv, ag[k].y);
+            ag[k].z = __builtin_fmaf(d[k].z * c[k].z, inv, ag[k].z); ag[k].w = __builtin_fmaf(d[k].w * c[k].w, inv, ag[k].w);
+            ab[k].x += d[k].x; ab[k].y += d[k].y; ab[k].z += d[k].z; ab[k].w += d[k].w;
+        }
+    }
+};
+
+template <bool DY16, int LPX, int NV, bool ACC, int U>      // C == 4 LPX NV; x / dx / dx_in rows 16-byte aligned, dy rows 8 (bf16) or 16
+__global__ __launch_bounds__(256) void chan_ln_bwd_pipe_kernel(const LnArgs a) {
+    MI_PRIO_UP();
+    constexpr int PPW = 64 / LPX;
+    __shared__ float red[2][4][LPX * NV * 4];
+    const int l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lp = l % LPX;
+    f32x4 ag[NV], ab[NV], gg[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        ag[k] = ab[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+        gg[k] = *reinterpret_cast<const f32x4*>(a.g + 4 * (lp + LPX * k));
+    }
+    const int step = gridDim.x * 4 * PPW;                 // pixels between two groups of a wave
+    int m0 = (blockIdx.x * 4 + w) * PPW;
+    // U groups at once while the first pixel of all of them exists (the same for every lane of the wave)
+    for (; a.M - m0 > (U - 1) * step; m0 += U * step) {
+        LnGroup<DY16, LPX, NV, ACC> grp[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) grp[u].load(a, m0 + u * step, l, lp);
+#pragma unroll
+        for (int u = 0; u < U; ++u) grp[u].finish(a, lp, gg, ag, ab);
+    }
+    for (; m0 < a.M; m0 += step) {
+        LnGroup<DY16, LPX, NV, ACC> grp;
+        grp.load(a, m0, l, lp);
+        grp.finish(a, lp, gg, ag, ab);
+    }
+    // the end of chan_ln_bwd_kernel: the pixel halves of a wave, then the 4 waves' per-channel partials in the same order
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        if constexpr (PPW == 2) {
+            ag[k].x += __shfl_xor(ag[k].x, 32, 64); ag[k].y += __shfl_xor(ag[k].y, 32, 64); ag[k].z += __shfl_xor(ag[k].z, 32, 64); ag[k].w += __shfl_xor(ag[k].w, 32, 64);
+            ab[k].x += __shfl_xor(ab[k].x, 32, 64); ab[k].y += __shfl_xor(ab[k].y, 32, 64); ab[k].z += __shfl_xor(ab[k].z, 32, 64); ab[k].w += __shfl_xor(ab[k].w, 32, 64);
+        }
+        const int q = lp + LPX * k;
+        if (l < LPX) {
+            red[0][w][4 * q + 0] = ag[k].x; red[0][w][4 * q + 1] = ag[k].y; red[0][w][4 * q + 2] = ag[k].z; red[0][w][4 * q + 3] = ag[k].w;
+            red[1][w][4 * q + 0] = ab[k].x; red[1][w][4 * q + 1] = ab[k].y; red[1][w][4 * q + 2] = ab[k].z; red[1][w][4 * q + 3] = ab[k].w;
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < a.C; c += 256) {
+        float v0 = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+        float v1 = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+        if (a.part) {
+            a.part[(size_t)blockIdx.x * 2 * a.C + c] = v0;
+            a.part[(size_t)blockIdx.x * 2 * a.C + a.C + c] = v1;
+        } else {
+            if (a.dg) atomicAdd(a.dg + c, v0);
+            if (a.db) atomicAdd(a.db + c, v1);
+        }
+    }
+}
+
 }  // namespace
 
 // 8-channel lanes: bf16 tensors only (a lane's 8 channels are one 16-byte access), every stride a multiple of 8 elements, slices
@@ -1171,6 +1311,21 @@ static int ln_bwd_blocks(int M, int C) {
     const int blocks = (M + (half ? 7 : 3)) / (half ? 8 : 4);
     return blocks > cap ? cap : blocks;
 }
+// chan_ln_bwd_pipe_kernel takes the launch when C is exactly one of its three widths and every row is aligned for its vector loads
+// (pitches are multiples of 4 elements for every launch); everything else runs chan_ln_bwd_kernel as before.
+static int g_ln_pipe = 1;             // tests / A-B: 0 = chan_ln_bwd_kernel for every launch
+extern "C" int mi_debug_ln_bwd_pipeline(int on) {
+    const int was = g_ln_pipe;
+    g_ln_pipe = on != 0;
+    return was;
+}
+extern "C" int mi_chan_layernorm_bwd_pipelined(int C, const void* x, const void* dy, const void* dx, const void* dx_in, int ldx, int lddy,
+                                               int lddx, int lddx_in, int dy16) {
+    if (!g_ln_pipe || (C != 128 && C != 256 && C != 512)) return 0;
+    if (ldx % 4 || lddy % 4 || lddx % 4 || (dx_in && lddx_in % 4)) return 0;
+    if (((uintptr_t)x | (uintptr_t)dx | (uintptr_t)dx_in) & 15) return 0;
+    return ((uintptr_t)dy & (dy16 ? 7 : 15)) == 0;
+}
 extern "C" int mi_chan_layernorm_bwd(int M, int C, const float* x, int ldx, const float* g, float eps,
                                      const float* dy, int lddy, float* dx, int lddx, int accumulate_dx,
                                      float* dg, float* db, void* stream) {
@@ -1221,6 +1376,20 @@ static int ln_bwd_go(int M, int C, const float* x, int ldx, const float* g, floa
     const bool half = C <= 128;                       // two pixels per wave
     const int blocks = ln_bwd_blocks(M, C);
     hipStream_t st = (hipStream_t)stream;
+    if (mi_chan_layernorm_bwd_pipelined(C, x, dy, dx, accumulate_dx ? a.dx_in : nullptr, ldx, lddy, lddx, a.lddx_in, dy16)) {
+        // groups in flight per width: 4, 4, 2 -- the faster of 2 and 4 in the training step's trace (docs/history/ln_bwd_pipeline.md)
+#define LN_PIPE_GO(DY16, LPX, NV, U)                                                                                                   \
+        do {                                                                                                                           \
+            if (accumulate_dx) hipLaunchKernelGGL((chan_ln_bwd_pipe_kernel<DY16, LPX, NV, true, U>), dim3(blocks), dim3(256), 0, st, a);  \
+            else               hipLaunchKernelGGL((chan_ln_bwd_pipe_kernel<DY16, LPX, NV, false, U>), dim3(blocks), dim3(256), 0, st, a); \
+        } while (0)
+        if (C == 128)      { if (dy16) LN_PIPE_GO(true, 32, 1, 4); else LN_PIPE_GO(false, 32, 1, 4); }
+        else if (C == 256) { if (dy16) LN_PIPE_GO(true, 64, 1, 4); else LN_PIPE_GO(false, 64, 1, 4); }
+        else               { if (dy16) LN_PIPE_GO(true, 64, 2, 2); else LN_PIPE_GO(false, 64, 2, 2); }
+#undef LN_PIPE_GO
+        MI_LAUNCH_CHECK();
+        return 0;
+    }
     if (half) { if (dy16) hipLaunchKernelGGL((chan_ln_bwd_kernel<true, 32, 1>), dim3(blocks), dim3(256), 0, st, a);
                 else      hipLaunchKernelGGL((chan_ln_bwd_kernel<false, 32, 1>), dim3(blocks), dim3(256), 0, st, a); }
     else      { if (dy16) hipLaunchKernelGGL((chan_ln_bwd_kernel<true, 64, 4>), dim3(blocks), dim3(256), 0, st, a);

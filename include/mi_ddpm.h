@@ -555,6 +555,12 @@ int mi_chan_layernorm_bwd_part(int M, int C, const float* x, int ldx, const floa
 int mi_chan_layernorm_bwd_out(int M, int C, const float* x, int ldx, const float* g, float eps,
                               const void* dy, int lddy, const float* dx_in, int lddx_in, float* dx_out, int lddx_out,
                               float* dg, float* db, float* part, int dy16, void* stream);
+/* 1 if the four backward entry points above run these pointers and pitches on the pipelined kernel (C = 128, 256 or 512, x / dx /
+ * dx_in 16-byte aligned, dy 8-byte (bf16) or 16-byte aligned: several pixel groups of a wave in flight, the same bits), 0 if on the
+ * guarded one.  dx_in: NULL when nothing is accumulated, dx itself for the accumulating in-place calls. */
+int mi_chan_layernorm_bwd_pipelined(int C, const void* x, const void* dy, const void* dx, const void* dx_in, int ldx, int lddy,
+                                    int lddx, int lddx_in, int dy16);
+int mi_debug_ln_bwd_pipeline(int on);           /* tests / A-B switch: 0 = the guarded kernel for every launch, anything else = the pipelined one where it applies (default); returns the previous value (0 or 1) */
 
 /* ---- LinearAttention core (ddpm.py:157-165), heads x 32 channels -------------------------
  * qkv[b][p][3*heads*32] (q | k | v, head-major inside each), out[b][p][heads*32].
