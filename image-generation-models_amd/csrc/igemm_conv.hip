@@ -567,6 +567,7 @@ int launch_fast(const IgemmArgs& a, const FastTaps& tt, int classes, bool in16, 
 
 static int igemm_dispatch(const MiConvDesc* d, const float* x, const float* x2, const float* w, const uint16_t* wb,
                           const float* bias, const float* residual, float* y, void* stream, bool in16 = false);
+static int igemm_plan(const MiConvDesc* d, bool has_wb, bool in16, bool vecA, MiIgemmPlan* p, FastTaps* tt);
 
 extern "C" int mi_conv_igemm(const MiConvDesc* d, const float* x, const float* x2, const float* w,
                              const float* bias, const float* residual, float* y, void* stream) {
@@ -588,7 +589,8 @@ extern "C" int mi_conv_igemm_bf16w_io_supported(const MiConvDesc* d) {
     if (!d || d->mode != 1 || d->K % 64 || d->K1 % 64 || d->ldx % 8 || (d->K1 != d->K && d->ldx2 % 8)) return 0;
     if (d->KH * d->KW > 16 || d->KH * d->KW == 1) return 0;
     if (d->transposed && d->stride > 1 && (d->OH % d->stride || d->OW % d->stride || d->stride != 2)) return 0;
-    return 1;
+    MiIgemmPlan p;                      // ... and the dispatch's own plan for aligned operands must be the ring kernel
+    return igemm_plan(d, true, true, true, &p, nullptr) == 0 && p.kernel == 1;
 }
 extern "C" int mi_conv_igemm_bf16w_io(const MiConvDesc* d, const void* x, const void* x2, const void* w_nk_bf16,
                                       const float* bias, const float* residual, float* y, int x_is_bf16, void* stream) {
@@ -599,92 +601,134 @@ extern "C" int mi_conv_igemm_bf16w_io(const MiConvDesc* d, const void* x, const 
     return igemm_dispatch(d, (const float*)x, (const float*)x2, (const float*)w_nk_bf16, (const uint16_t*)w_nk_bf16, bias, residual, y, stream, true);
 }
 
-static int igemm_dispatch(const MiConvDesc* d, const float* x, const float* x2, const float* w, const uint16_t* wb,
-                          const float* bias, const float* residual, float* y, void* stream, bool in16) {
-    MI_REQUIRE(d && x && w && y, "null argument");
+// tile choice: keep >= ~2 workgroups per CU when the problem allows it
+static void igemm_tile_rule(int Mc, int Nc, int classes, bool* bm64, bool* bn64) {
+    long tiles128 = (long)((Mc + 127) / 128) * ((Nc + 127) / 128) * classes;
+    *bn64 = Nc <= 64;
+    *bm64 = tiles128 < 384 || Mc <= 64;
+    if (*bn64 == false && *bm64 && (long)((Mc + 63) / 64) * ((Nc + 127) / 128) * classes < 384) *bn64 = true;
+}
+
+// Everything the host decides from the descriptor alone: the checks on it, the parity classes, the k-slices, the tile and which
+// kernel runs.  igemm_dispatch launches what this says and mi_conv_igemm_plan reports it.  has_wb: the bf16 weight copy is given;
+// in16: bf16-stored activations; vecA: 16-byte activation loads are legal (pitches and pointers).  tt (optional): the ring
+// kernel's tap table.
+static int igemm_plan(const MiConvDesc* d, bool has_wb, bool in16, bool vecA, MiIgemmPlan* p, FastTaps* tt) {
+    MI_REQUIRE(d && p, "null argument");
     MI_REQUIRE(d->N > 0 && d->K > 0 && d->Nc > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0, "bad sizes");
     MI_REQUIRE(d->mode == 0 || d->mode == 1, "mode must be 0 (fp32) or 1 (bf16)");
-    MI_REQUIRE(d->K1 == d->K || (x2 && d->K1 > 0 && d->K1 < d->K && d->K1 % 4 == 0), "bad two-source split");
+    MI_REQUIRE(d->K1 == d->K || (d->K1 > 0 && d->K1 < d->K && d->K1 % 4 == 0), "bad two-source split");
     MI_REQUIRE(d->ldx % 4 == 0 && d->ldy >= d->Nc, "ldx must be a multiple of 4, ldy >= Nc");
     MI_REQUIRE(!in16 || d->K1 == d->K || d->K1 % 64 == 0, "bf16 activations: K1 % 64 == 0");
-    IgemmArgs a;
-    a.x = x; a.x2 = x2 ? x2 : x; a.w = w; a.wb = wb; a.bias = bias; a.res = residual; a.y = y;
-    a.N = d->N; a.IH = d->IH; a.IW = d->IW; a.OH = d->OH; a.OW = d->OW; a.K = d->K; a.Nc = d->Nc;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.transposed = d->transposed;
-    a.w_kn = d->w_kn; a.K1 = d->K1; a.ldx = d->ldx; a.ldx2 = x2 ? d->ldx2 : d->ldx; a.ldy = d->ldy;
-    a.ldr = d->ldr; a.accumulate = d->accumulate;
-    int classes = 1;
-    a.OHc = d->OH; a.OWc = d->OW;
+    const int s = d->stride;
+    int classes = 1, OHc = d->OH, OWc = d->OW;
     bool ragged = false;                      // output extent not a multiple of the stride (7x7 from 4x4, stride 2): rows of the
-    if (d->transposed && d->stride > 1) {     // last partial class cell are computed and dropped at the store
-        MI_REQUIRE(d->KH >= d->stride && d->KW >= d->stride, "transposed: kernel smaller than stride");
-        classes = d->stride * d->stride;
-        a.OHc = (d->OH + d->stride - 1) / d->stride; a.OWc = (d->OW + d->stride - 1) / d->stride;
-        ragged = d->OH % d->stride != 0 || d->OW % d->stride != 0;
+    if (d->transposed && s > 1) {             // last partial class cell are computed and dropped at the store
+        MI_REQUIRE(d->KH >= s && d->KW >= s, "transposed: kernel smaller than stride");
+        classes = s * s;
+        OHc = (d->OH + s - 1) / s; OWc = (d->OW + s - 1) / s;
+        ragged = d->OH % s != 0 || d->OW % s != 0;
     }
-    a.Mc = d->N * a.OHc * a.OWc;
-    // activations: rows are 16-B aligned when ld % 4 == 0; a chunk may still be ragged at the end
-    a.vecA = (d->ldx % 4 == 0) && (a.ldx2 % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)a.x2 & 15) == 0);
-    a.vecB = (((uintptr_t)w & 15) == 0) && (d->w_kn ? (d->Nc % 4 == 0) : (d->K % 4 == 0));
-    if (residual) MI_REQUIRE(d->ldr >= d->Nc, "ldr < Nc");
-    hipStream_t st = (hipStream_t)stream;
-    a.ksplit = 1;
+    const int Mc = d->N * OHc * OWc;
+    int ksplit = 1;
     {   // long contraction, almost no tiles (Linear dgrad of the fused time-bias GEMM): split the channel axis
-        long tiles64 = (long)((a.Mc + 63) / 64) * ((d->Nc + 63) / 64) * classes;
+        long tiles64 = (long)((Mc + 63) / 64) * ((d->Nc + 63) / 64) * classes;
         if (tiles64 <= 16 && d->K >= 1024 && d->KH * d->KW == 1 && (d->accumulate || d->ldy == d->Nc)) {
-            int ks = d->K / 128; if (ks > 32) ks = 32;
-            a.ksplit = ks;
-            if (!d->accumulate) {
-                hipError_t e = mi_zero_async(y, (size_t)d->N * d->OH * d->OW * d->ldy * sizeof(float), st);
-                if (e != hipSuccess) return mi_set_error((int)e, "mi_conv_igemm: memset: %s", hipGetErrorString(e));
-            }
+            ksplit = d->K / 128; if (ksplit > 32) ksplit = 32;
         }
     }
-
-    // tile choice: keep >= ~2 workgroups per CU when the problem allows it
-    long tiles128 = (long)((a.Mc + 127) / 128) * ((d->Nc + 127) / 128) * classes;
-    bool bn64 = d->Nc <= 64;
-    bool bm64 = tiles128 < 384 || a.Mc <= 64;
-    if (bn64 == false && bm64 && (long)((a.Mc + 63) / 64) * ((d->Nc + 127) / 128) * classes < 384) bn64 = true;
+    bool bm64, bn64;
+    igemm_tile_rule(Mc, d->Nc, classes, &bm64, &bn64);
+    p->kernel = 0; p->classes = classes; p->ragged = ragged; p->ksplit = ksplit;
+    // taps per class, as igemm_kernel's tap_ok and the ring kernel's table see them
+    FastTaps local;
+    FastTaps& t = tt ? *tt : local;
+    bool table_ok = classes <= 4 && d->KH * d->KW <= 16;
+    for (int c = 0; c < classes; ++c) {
+        const int py = d->transposed ? c / s : 0, px = d->transposed ? c % s : 0;
+        int nt = 0;
+        for (int ky = 0; ky < d->KH; ++ky)
+            for (int kx = 0; kx < d->KW; ++kx) {
+                int dy, dx;
+                if (d->transposed) {
+                    const int ny = py + d->pad - ky, nx = px + d->pad - kx;
+                    if (((ny % s) + s) % s || ((nx % s) + s) % s) continue;
+                    dy = ny / s; dx = nx / s;
+                } else { dy = ky - d->pad; dx = kx - d->pad; }
+                if (table_ok && nt < 16) {
+                    t.dy[c * 16 + nt] = dy; t.dx[c * 16 + nt] = dx; t.dpix[c * 16 + nt] = dy * d->IW + dx;
+                    t.tap[c * 16 + nt] = ky * d->KW + kx;
+                }
+                ++nt;
+            }
+        if (c < 4) t.ntap[c] = nt;
+        if (nt == 0) table_ok = false;
+        if (c < MI_IGEMM_PLAN_CLASSES) p->ntap[c] = nt;
+    }
     // aligned bf16 layers with few taps per class: the straight-line ring kernel
     static const int allow_fast = (int)mi_knob("MI_IGEMM_FAST", 1);
     // (bf16-stored activations exist only on the ring kernel: the profiling switch does not apply to them, so that
     //  mi_conv_igemm_bf16w_io_supported() and this dispatch agree)
-    if ((allow_fast || in16) && !ragged && d->mode == 1 && wb && a.ksplit == 1 && d->K % 32 == 0 && d->K1 % 32 == 0 && a.vecA && classes <= 4 &&
-        d->KH * d->KW <= 16) {
-        FastTaps tt;
-        bool ok = true;
-        for (int c = 0; c < classes && ok; ++c) {
-            const int py = d->transposed ? c / d->stride : 0, px = d->transposed ? c % d->stride : 0;
-            int nt = 0;
-            for (int ky = 0; ky < d->KH; ++ky)
-                for (int kx = 0; kx < d->KW; ++kx) {
-                    int dy, dx;
-                    if (d->transposed) {
-                        const int ny = py + d->pad - ky, nx = px + d->pad - kx;
-                        if (((ny % d->stride) + d->stride) % d->stride || ((nx % d->stride) + d->stride) % d->stride) continue;
-                        dy = ny / d->stride; dx = nx / d->stride;
-                    } else { dy = ky - d->pad; dx = kx - d->pad; }
-                    if (nt >= 16) { ok = false; break; }
-                    tt.dy[c * 16 + nt] = dy; tt.dx[c * 16 + nt] = dx; tt.dpix[c * 16 + nt] = dy * d->IW + dx;
-                    tt.tap[c * 16 + nt] = ky * d->KW + kx;
-                    ++nt;
-                }
-            tt.ntap[c] = nt;
-            if (nt == 0) ok = false;
-        }
-        if (ok) {
-            static const int force = (int)mi_knob("MI_IGEMM_TILE", 0);   // 11 / 10 / 01 / 00 = bm64,bn64 (profiling)
-            if (force) { bm64 = (force / 10) % 10 == 1; bn64 = force % 10 == 1; if (force == 100) { bm64 = false; bn64 = false; } }
-            if (!bm64 && !bn64) launch_fast<128, 128>(a, tt, classes, in16, st);
-            else if (!bm64 && bn64) launch_fast<128, 64>(a, tt, classes, in16, st);
-            else if (bm64 && !bn64) launch_fast<64, 128>(a, tt, classes, in16, st);
-            else launch_fast<64, 64>(a, tt, classes, in16, st);
-            MI_LAUNCH_CHECK();
-            return 0;
-        }
+    if ((allow_fast || in16) && !ragged && d->mode == 1 && has_wb && ksplit == 1 && d->K % 32 == 0 && d->K1 % 32 == 0 && vecA && table_ok) {
+        static const int force = (int)mi_knob("MI_IGEMM_TILE", 0);   // 11 / 10 / 01 / 00 = bm64,bn64 (profiling)
+        if (force) { bm64 = (force / 10) % 10 == 1; bn64 = force % 10 == 1; if (force == 100) { bm64 = false; bn64 = false; } }
+        p->kernel = 1;
     }
-    MI_REQUIRE(!in16, "bf16 activations: the layer does not fit the ring kernel (mi_conv_igemm_bf16w_io_supported)");
+    MI_REQUIRE(!in16 || p->kernel == 1, "bf16 activations: the layer does not fit the ring kernel (mi_conv_igemm_bf16w_io_supported)");
+    p->bm = bm64 ? 64 : 128; p->bn = bn64 ? 64 : 128;
+    const int ck = p->kernel == 1 && in16 ? 64 : 32;          // channels per stage
+    for (int c = 0; c < MI_IGEMM_PLAN_CLASSES; ++c) {
+        if (c >= classes) p->ntap[c] = 0;
+        p->stages[c] = p->ntap[c] * ((d->K + ck - 1) / ck);
+    }
+    return 0;
+}
+
+extern "C" int mi_conv_igemm_plan(const MiConvDesc* d, int has_wb, int in16, int aligned, MiIgemmPlan* plan) {
+    MI_REQUIRE(d && plan, "null argument");
+    const bool vecA = aligned && d->ldx % 4 == 0 && (d->K1 == d->K || d->ldx2 % 4 == 0);
+    return igemm_plan(d, has_wb != 0, in16 != 0, vecA, plan, nullptr);
+}
+
+static int igemm_dispatch(const MiConvDesc* d, const float* x, const float* x2, const float* w, const uint16_t* wb,
+                          const float* bias, const float* residual, float* y, void* stream, bool in16) {
+    MI_REQUIRE(d && x && w && y, "null argument");
+    const int ldx2 = x2 ? d->ldx2 : d->ldx;
+    const float* xs = x2 ? x2 : x;
+    // activations: rows are 16-B aligned when ld % 4 == 0; a chunk may still be ragged at the end
+    const bool vecA = (d->ldx % 4 == 0) && (ldx2 % 4 == 0) && (((uintptr_t)x & 15) == 0) && (((uintptr_t)xs & 15) == 0);
+    MiIgemmPlan p;
+    FastTaps tt;
+    if (int rc = igemm_plan(d, wb != nullptr, in16, vecA, &p, &tt)) return rc;
+    MI_REQUIRE(d->K1 == d->K || x2, "bad two-source split");
+    if (residual) MI_REQUIRE(d->ldr >= d->Nc, "ldr < Nc");
+    IgemmArgs a;
+    a.x = x; a.x2 = xs; a.w = w; a.wb = wb; a.bias = bias; a.res = residual; a.y = y;
+    a.N = d->N; a.IH = d->IH; a.IW = d->IW; a.OH = d->OH; a.OW = d->OW; a.K = d->K; a.Nc = d->Nc;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.transposed = d->transposed;
+    a.w_kn = d->w_kn; a.K1 = d->K1; a.ldx = d->ldx; a.ldx2 = ldx2; a.ldy = d->ldy;
+    a.ldr = d->ldr; a.accumulate = d->accumulate;
+    const int classes = p.classes;
+    a.OHc = d->OH; a.OWc = d->OW;
+    if (classes > 1) { a.OHc = (d->OH + d->stride - 1) / d->stride; a.OWc = (d->OW + d->stride - 1) / d->stride; }
+    a.Mc = d->N * a.OHc * a.OWc;
+    a.vecA = vecA;
+    a.vecB = (((uintptr_t)w & 15) == 0) && (d->w_kn ? (d->Nc % 4 == 0) : (d->K % 4 == 0));
+    hipStream_t st = (hipStream_t)stream;
+    a.ksplit = p.ksplit;
+    if (a.ksplit > 1 && !d->accumulate) {     // the k-slices add atomically
+        hipError_t e = mi_zero_async(y, (size_t)d->N * d->OH * d->OW * d->ldy * sizeof(float), st);
+        if (e != hipSuccess) return mi_set_error((int)e, "mi_conv_igemm: memset: %s", hipGetErrorString(e));
+    }
+    const bool bm64 = p.bm == 64, bn64 = p.bn == 64;
+    if (p.kernel == 1) {
+        if (!bm64 && !bn64) launch_fast<128, 128>(a, tt, classes, in16, st);
+        else if (!bm64 && bn64) launch_fast<128, 64>(a, tt, classes, in16, st);
+        else if (bm64 && !bn64) launch_fast<64, 128>(a, tt, classes, in16, st);
+        else launch_fast<64, 64>(a, tt, classes, in16, st);
+        MI_LAUNCH_CHECK();
+        return 0;
+    }
 #define MI_GO(MODE) \
     do { if (!bm64 && !bn64) launch<MODE, 128, 128>(a, classes, st); \
          else if (!bm64 && bn64) launch<MODE, 128, 64>(a, classes, st); \
@@ -701,11 +745,8 @@ extern "C" int mi_conv_igemm_tile(const MiConvDesc* d, int* bm, int* bn) {
     MI_REQUIRE(d && bm && bn, "null argument");
     int classes = 1, OHc = d->OH, OWc = d->OW;
     if (d->transposed && d->stride > 1) { classes = d->stride * d->stride; OHc = (OHc + d->stride - 1) / d->stride; OWc = (OWc + d->stride - 1) / d->stride; }
-    int Mc = d->N * OHc * OWc;
-    long tiles128 = (long)((Mc + 127) / 128) * ((d->Nc + 127) / 128) * classes;
-    bool bn64 = d->Nc <= 64;
-    bool bm64 = tiles128 < 384 || Mc <= 64;
-    if (bn64 == false && bm64 && (long)((Mc + 63) / 64) * ((d->Nc + 127) / 128) * classes < 384) bn64 = true;
+    bool bm64, bn64;
+    igemm_tile_rule(d->N * OHc * OWc, d->Nc, classes, &bm64, &bn64);
     *bm = bm64 ? 64 : 128; *bn = bn64 ? 64 : 128;
     return 0;
 }

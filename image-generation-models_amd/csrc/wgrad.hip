@@ -382,10 +382,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_fast_kernel(const WgradArgs a, i
 }
 
 template <int BI, int BJ>
-void launch_fast(WgradArgs a, int dw_sh, int dhw_sh, hipStream_t st) {
-    static const int xcd_env = (int)mi_knob("MI_WGRAD_XCD", 1);
-    a.gx = (a.Ci + BI - 1) / BI; a.gy = (a.Cj + BJ - 1) / BJ;
-    a.xcd_map = xcd_env && a.splits >= 8;
+void launch_fast(const WgradArgs& a, int dw_sh, int dhw_sh, hipStream_t st) {     // a.gx, a.gy, a.xcd_map: from wgrad_plan
     dim3 grid(a.gx, a.gy, a.KH * a.KW * a.splits);
     if (a.xcd_map) grid = dim3((unsigned)(a.gx * a.gy * a.KH * a.KW * ((a.splits + 7) / 8 * 8)), 1, 1);
     hipLaunchKernelGGL((wgrad_fast_kernel<BI, BJ>), grid, dim3(256), 0, st, a, dw_sh, dhw_sh);
@@ -430,6 +427,41 @@ static int wgrad_plan_splits(const MiWgradDesc* d, int* chunk) {
     return (Mtot + ch - 1) / ch;
 }
 
+static int ilog2_exact(int v) { int s = 0; while (s < 30 && (1 << s) < v) ++s; return (1 << s) == v ? s : -1; }
+
+// Everything the host decides from the descriptor alone: the checks on it, the pixel slices, the tile and which kernel runs.
+// conv_wgrad_impl launches what this says and mi_conv_wgrad_plan reports it.  vec: 16-byte loads are legal (pitches and
+// pointers); slab: the slab mode (generic kernel only).
+static int wgrad_plan(const MiWgradDesc* d, bool vec, bool slab, MiWgradPlan* p) {
+    MI_REQUIRE(d && p, "null argument");
+    MI_REQUIRE(d->N > 0 && d->DH > 0 && d->DW > 0 && d->Ci > 0 && d->Cj > 0 && d->KH > 0 && d->KW > 0, "bad sizes");
+    MI_REQUIRE(d->mode == 0 || d->mode == 1, "mode must be 0 or 1");
+    MI_REQUIRE(d->I1 == d->Ci || (d->I1 > 0 && d->I1 < d->Ci && d->I1 % 4 == 0), "bad two-source split");
+    p->big = d->Ci >= 128 && d->Cj >= 128;
+    p->splits = wgrad_plan_splits(d, &p->chunk);
+    const int B = p->big ? 128 : 64;
+    const int gx = (d->Ci + B - 1) / B, gy = (d->Cj + B - 1) / B;
+    p->fast = 0; p->xcd_map = 0;
+    p->grid = gx * gy * d->KH * d->KW * p->splits;
+    if (!slab) {   // aligned bf16 layers on a power-of-two dense grid: the straight-line ring kernel
+        static const int allow_fast = (int)mi_knob("MI_WGRAD_FAST", 1);
+        static const int xcd_env = (int)mi_knob("MI_WGRAD_XCD", 1);
+        if (allow_fast && d->mode == 1 && vec && ilog2_exact(d->DW) >= 0 && ilog2_exact(d->DH * d->DW) >= 0 && d->Ci % 4 == 0 && d->Cj % 4 == 0 &&
+            d->I1 % 4 == 0 && d->Ci >= 4 && d->Cj >= 4) {
+            p->fast = 1;
+            p->xcd_map = xcd_env && p->splits >= 8;
+            if (p->xcd_map) p->grid = gx * gy * d->KH * d->KW * ((p->splits + 7) / 8 * 8);
+        }
+    }
+    return 0;
+}
+
+extern "C" int mi_conv_wgrad_plan(const MiWgradDesc* d, int aligned, int slab, MiWgradPlan* plan) {
+    MI_REQUIRE(d && plan, "null argument");
+    const bool vec = aligned && d->ldp % 4 == 0 && (d->I1 == d->Ci || d->ldp2 % 4 == 0) && d->ldq % 4 == 0;
+    return wgrad_plan(d, vec, slab != 0, plan);
+}
+
 static int conv_wgrad_impl(const MiWgradDesc* d, const float* P, const float* P2, const float* Q, float* dW, float* slab, void* stream);
 
 extern "C" int mi_conv_wgrad(const MiWgradDesc* d, const float* P, const float* P2, const float* Q,
@@ -451,30 +483,31 @@ extern "C" int mi_conv_wgrad_slabs(const MiWgradDesc* d, const float* P, const f
 
 static int conv_wgrad_impl(const MiWgradDesc* d, const float* P, const float* P2, const float* Q, float* dW, float* slab, void* stream) {
     MI_REQUIRE(d && P && Q && dW, "null argument");
-    MI_REQUIRE(d->mode == 0 || d->mode == 1, "mode must be 0 or 1");
-    MI_REQUIRE(d->I1 == d->Ci || (P2 && d->I1 > 0 && d->I1 < d->Ci && d->I1 % 4 == 0), "bad two-source split");
+    const int ldp2 = P2 ? d->ldp2 : d->ldp;
+    const float* Ps = P2 ? P2 : P;
+    const bool vec = (d->ldp % 4 == 0) && (ldp2 % 4 == 0) && (d->ldq % 4 == 0) && (((uintptr_t)P & 15) == 0) &&
+                     (((uintptr_t)Ps & 15) == 0) && (((uintptr_t)Q & 15) == 0);
+    MiWgradPlan p;
+    if (int rc = wgrad_plan(d, vec, slab != nullptr, &p)) return rc;
+    MI_REQUIRE(d->I1 == d->Ci || P2, "bad two-source split");
     WgradArgs a;
-    a.P = P; a.P2 = P2 ? P2 : P; a.Q = Q; a.dW = dW;
+    a.P = P; a.P2 = Ps; a.Q = Q; a.dW = dW;
     a.N = d->N; a.GH = d->GH; a.GW = d->GW; a.DH = d->DH; a.DW = d->DW; a.Ci = d->Ci; a.Cj = d->Cj;
     a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.gather_i = d->gather_i;
-    a.I1 = d->I1; a.ldp = d->ldp; a.ldp2 = P2 ? d->ldp2 : d->ldp; a.ldq = d->ldq;
+    a.I1 = d->I1; a.ldp = d->ldp; a.ldp2 = ldp2; a.ldq = d->ldq;
     a.Mtot = d->N * d->DH * d->DW;
     a.xcd_map = 0; a.gx = a.gy = 0; a.slab = slab;
-    a.vec = (d->ldp % 4 == 0) && (a.ldp2 % 4 == 0) && (d->ldq % 4 == 0) && (((uintptr_t)P & 15) == 0) &&
-            (((uintptr_t)a.P2 & 15) == 0) && (((uintptr_t)Q & 15) == 0);
-    const bool big = d->Ci >= 128 && d->Cj >= 128;
-    a.splits = wgrad_plan_splits(d, &a.chunk);
+    a.vec = vec;
+    const bool big = p.big;
+    a.splits = p.splits; a.chunk = p.chunk;
     hipStream_t st = (hipStream_t)stream;
-    if (!slab) {   // aligned bf16 layers on a power-of-two dense grid: the straight-line ring kernel
-        static const int allow_fast = (int)mi_knob("MI_WGRAD_FAST", 1);
-        auto lg = [](int v) { int s = 0; while ((1 << s) < v) ++s; return (1 << s) == v ? s : -1; };
-        const int dw_sh = lg(d->DW), dhw_sh = lg(d->DH * d->DW);
-        if (allow_fast && d->mode == 1 && a.vec && dw_sh >= 0 && dhw_sh >= 0 && d->Ci % 4 == 0 && d->Cj % 4 == 0 && d->I1 % 4 == 0 &&
-            d->Ci >= 4 && d->Cj >= 4) {
-            if (big) launch_fast<128, 128>(a, dw_sh, dhw_sh, st); else launch_fast<64, 64>(a, dw_sh, dhw_sh, st);
-            MI_LAUNCH_CHECK();
-            return 0;
-        }
+    if (p.fast) {
+        const int B = big ? 128 : 64;
+        a.gx = (a.Ci + B - 1) / B; a.gy = (a.Cj + B - 1) / B; a.xcd_map = p.xcd_map;
+        const int dw_sh = ilog2_exact(d->DW), dhw_sh = ilog2_exact(d->DH * d->DW);
+        if (big) launch_fast<128, 128>(a, dw_sh, dhw_sh, st); else launch_fast<64, 64>(a, dw_sh, dhw_sh, st);
+        MI_LAUNCH_CHECK();
+        return 0;
     }
     if (d->mode == 1) { if (big) launch<1, 128, 128>(a, st); else launch<1, 64, 64>(a, st); }
     else              { if (big) launch<0, 128, 128>(a, st); else launch<0, 64, 64>(a, st); }

@@ -27,6 +27,18 @@ class MiWgradDesc(C.Structure):
         "ldp", "ldp2", "ldq")]
 
 
+IGEMM_PLAN_CLASSES = 16   # MI_IGEMM_PLAN_CLASSES
+
+
+class MiIgemmPlan(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("kernel", "bm", "bn", "classes", "ragged", "ksplit")]
+                + [("ntap", C.c_int * IGEMM_PLAN_CLASSES), ("stages", C.c_int * IGEMM_PLAN_CLASSES)])
+
+
+class MiWgradPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("fast", "big", "splits", "chunk", "xcd_map", "grid")]
+
+
 class MiGnDesc(C.Structure):
     _fields_ = [("N", C.c_int), ("HW", C.c_int), ("C", C.c_int), ("G", C.c_int), ("eps", C.c_float),
                 ("ldx", C.c_int), ("ldy", C.c_int), ("ldr", C.c_int)]
@@ -62,6 +74,8 @@ SIGNATURES = {
     "mi_conv_gt": [C.POINTER(MiConvDesc), _P, _P, _P, _P, _P, _I, _P],
     "mi_conv_gt_dual": [C.POINTER(MiConvDesc), _P, _P, _P, _P, _P, _P, _I, _P],
     "mi_conv_igemm_tile": [C.POINTER(MiConvDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "mi_conv_igemm_plan": [C.POINTER(MiConvDesc), _I, _I, _I, C.POINTER(MiIgemmPlan)],
+    "mi_conv_wgrad_plan": [C.POINTER(MiWgradDesc), _I, _I, C.POINTER(MiWgradPlan)],
     "mi_conv3x3_bf16w": [C.POINTER(MiConvDesc), _P, _P, _P, _P, _P, _P, _P],
     "mi_conv3x3_bf16w_supported": [C.POINTER(MiConvDesc)],
     "mi_conv3x3_bf16w_uses_splitk": [C.POINTER(MiConvDesc)],

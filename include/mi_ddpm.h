@@ -81,6 +81,23 @@ int mi_conv_igemm_bf16w_io(const MiConvDesc* d, const void* x, const void* x2, c
                            const float* bias, const float* residual, float* y, int x_is_bf16, void* stream);
 /* tile instantiation mi_conv_igemm will launch for d (BM x BN); used to attribute profiles */
 int mi_conv_igemm_tile(const MiConvDesc* d, int* bm, int* bn);
+/* What the dispatch behind mi_conv_igemm / _bf16w / _bf16w_io decides for d (read-only; the dispatch launches from the same function).
+ * has_wb: the bf16 weight copy is given; in16: bf16-stored activations; aligned: x, x2 are 16-byte aligned (the pitches are read from d).
+ * Returns non-zero with mi_last_error() set where the dispatch refuses the descriptor.
+ * A one-source descriptor (K1 == K) is planned as called with x2 == NULL: the dispatch reads d->ldx2 whenever x2 is given, so a
+ * one-source call that still passes an x2 with ldx2 % 4 != 0 loses its vector loads, which the query cannot see.
+ * mi_conv_igemm_bf16w_io_supported asks the same plan, so it too leaves the refusal's text in mi_last_error() when it answers 0. */
+#define MI_IGEMM_PLAN_CLASSES 16
+typedef struct MiIgemmPlan {
+    int kernel;                          /* 0 = igemm_kernel, 1 = igemm_fast_kernel (the register-ring kernel) */
+    int bm, bn;                          /* tile */
+    int classes;                         /* parity classes of a transposed conv with stride > 1 (stride^2), else 1 */
+    int ragged;                          /* output extent not a multiple of the stride: the last class cell is partly dropped */
+    int ksplit;                          /* slices of the channel axis; > 1: y is zeroed (unless accumulate) and the slices add atomically */
+    int ntap[MI_IGEMM_PLAN_CLASSES];     /* taps that contribute to class c (0 past `classes`) */
+    int stages[MI_IGEMM_PLAN_CLASSES];   /* ntap * ceil(K / CK): 32-channel steps (64 for the ring kernel on bf16 activations), all k-slices together */
+} MiIgemmPlan;
+int mi_conv_igemm_plan(const MiConvDesc* d, int has_wb, int in16, int aligned, MiIgemmPlan* plan);
 
 /* ---- tap-gather GEMM (round 4): the stride-2 Downsample conv (ddpm.py:79), the ConvTranspose2d(4, 2, 1) Upsample (ddpm.py:70) and
  * their data gradients for bf16-stored activations, same contract as mi_conv_igemm (d->transposed = 1: the parity classes of the
@@ -342,6 +359,18 @@ typedef struct MiWgradDesc {
 
 int mi_conv_wgrad(const MiWgradDesc* d, const float* P, const float* P2, const float* Q,
                   float* dW, void* stream);
+/* What mi_conv_wgrad (slab = 0) / mi_conv_wgrad_slabs (slab = 1) decide for d (read-only; the launch comes from the same function).
+ * aligned: P, P2 and Q are 16-byte aligned (the pitches are read from d).  Non-zero with mi_last_error() set where d is refused
+ * (non-positive sizes among the reasons: mi_conv_wgrad refuses them too).  As for the convolution, I1 == Ci is planned as called
+ * with P2 == NULL; the launch reads d->ldp2 whenever P2 is given. */
+typedef struct MiWgradPlan {
+    int fast;            /* 1 = wgrad_fast_kernel (the register-ring kernel), 0 = wgrad_kernel */
+    int big;             /* 128 x 128 channel tiles (Ci >= 128 and Cj >= 128), else 64 x 64 */
+    int splits, chunk;   /* slices of the pixel axis and pixels per slice (a multiple of 32) */
+    int xcd_map;         /* ring kernel: 1-D grid that keeps a slice's workgroups on one XCD (splits >= 8) */
+    int grid;            /* workgroups of the launch (with xcd_map: splits rounded up to 8, the surplus returns at once) */
+} MiWgradPlan;
+int mi_conv_wgrad_plan(const MiWgradDesc* d, int aligned, int slab, MiWgradPlan* plan);
 
 /* 3x3 / stride 1 / pad 1 Conv2d weight gradient on bf16 MFMA with image-major contraction vectors
  * (needs N % 8 == 0, channel counts % 32 == 0; query first, else use mi_conv_wgrad). */
