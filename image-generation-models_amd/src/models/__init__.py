@@ -1,6 +1,6 @@
 """Models with the reference's surface.  Import them from their modules (`src.models.ddpm`, `src.models.factor_vae`, ...), as the
 configs' `_target_`s do; `src.models.FactorVAE` and `src.models.AAE` are resolved lazily (the networks import `src.models.ddpm`, so
-nothing may be imported here at package load); `src.models.GAN`, `src.models.InfoGAN` and `src.models.AGE` likewise."""
+nothing may be imported here at package load); `src.models.GAN`, `src.models.InfoGAN`, `src.models.AGE` and `src.models.VAEGAN` likewise."""
 
 
 def __getattr__(name):
@@ -19,4 +19,7 @@ def __getattr__(name):
     if name == "AGE":
         from .age import AGE
         return AGE
+    if name == "VAEGAN":
+        from .vae_gan import VAEGAN
+        return VAEGAN
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

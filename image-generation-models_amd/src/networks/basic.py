@@ -113,14 +113,20 @@ class ConvDecoder(FlatNet, _NormMixin):
             tape.append(out)
         return out, tape
 
-    def backward_nhwc(self, tape, dy, need_dx=False, param_grads=True):
+    def backward_nhwc(self, tape, dy, need_dx=False, param_grads=True, own_dy=False):
         """param_grads=False: the input gradient only -- no weight, bias or affine gradient is computed and the gradient buffer is
-        left alone (the AGE's encoder phase sends its reconstruction gradient through the frozen decoder)."""
+        left alone (the AGE's encoder phase sends its reconstruction gradient through the frozen decoder).
+        own_dy: dy is a view of a dense buffer with the output's pixel pitch whose padded lanes are 0, and the caller gives it up:
+        the backward works in it instead of filling a copy (two launches less)."""
         gv = self._begin_backward() if param_grads else {}
         y = tape[-1]
         yb = y._base if y._base is not None else y
-        d = torch.zeros_like(yb)
-        d[..., :self.output_channel] = dy
+        db = dy._base if dy._base is not None else dy
+        if own_dy and db.shape == yb.shape and db.is_contiguous() and db.data_ptr() == dy.data_ptr():
+            d = db
+        else:
+            d = torch.zeros_like(yb)
+            d[..., :self.output_channel] = dy
         if self.output_act == "tanh":
             K.tanh_bwd(yb, d, out=d)
         g = d[..., :self.output_channel]
@@ -147,8 +153,9 @@ class ConvEncoder(FlatNet, _NormMixin):
     def __init__(self, input_channel, output_channel, ndf, norm_type="batch", return_features=False):
         super().__init__()
         _check_norm(norm_type)
-        if return_features:
-            raise NotImplementedError("feature extraction is used by the GAN zoo only")
+        # return_features (the VAE-GAN's netD): forward also returns the activation after network.7 -- the reference's FeatureExtractor
+        # hook, which holds no parameters, so the state-dict keys are the same either way
+        self.return_features = bool(return_features)
         self.input_channel, self.output_channel, self.norm_type = input_channel, output_channel, norm_type
         chans = [input_channel, ndf, ndf * 2, ndf * 4]
         for i, (pre, k, s, p, norm) in enumerate(self.CONVS):
@@ -159,7 +166,20 @@ class ConvEncoder(FlatNet, _NormMixin):
         self._finish()
 
     def forward(self, x):
+        if self.return_features:
+            # (output [N, C_out], features): the 1-D ravel of the NCHW [N, 4 ndf, 4, 4] activation after network.7, the reference's
+            # layout (basic.py:196-202).  Inference only: a training step drives forward_nhwc / backward_nhwc(dfeat=...) itself.
+            if not (torch.is_tensor(x) and x.is_cuda):
+                raise RuntimeError("libmi_ddpm kernels need tensors on an MI355X (HIP) device; there is no CPU fallback")
+            with torch.no_grad():
+                out, tape = self.forward_nhwc(K.nchw_to_nhwc(x.float()), record=True)
+                return out.reshape(-1, self.output_channel), K.nhwc_to_nchw(self.features_nhwc(tape)).reshape(-1)
         return super().forward(x).reshape(-1, self.output_channel)
+
+    @staticmethod
+    def features_nhwc(tape):
+        """The last hidden activation (after network.7) of a recorded forward: dense NHWC [rows, 4, 4, 4 ndf], the tape's own tensor."""
+        return tape[3][2]
 
     def forward_nhwc(self, x, record=False, bn_updates=1, segments=1):
         """bn_updates = u: the forward counts as u successive training-mode forwards of this batch for the BatchNorm running
@@ -186,11 +206,20 @@ class ConvEncoder(FlatNet, _NormMixin):
         out = self._conv(h, "network.8.", 4, 1, 0)
         return out, tape
 
-    def backward_nhwc(self, tape, dout, need_dx=False, param_grads=True):
+    def backward_nhwc(self, tape, dout, need_dx=False, param_grads=True, dfeat=None):
         """param_grads=False: the input gradient only -- no weight, bias or affine gradient is computed and the gradient buffer is
-        left alone (a GAN's generator phase needs nothing else from its discriminator)."""
+        left alone (a GAN's generator phase needs nothing else from its discriminator).
+        dfeat: a gradient by the last hidden activation (`features_nhwc`), added to what network.8's input-gradient conv produced
+        before the norm + activation backward: a tensor of that shape, or a callable that adds into the buffer it is handed (the
+        VAE-GAN's K.feat_match with accumulate, which touches the recon segment's rows alone)."""
         gv = self._begin_backward() if param_grads else {}
         g = self._conv_bwd(dout, tape[3][2], "network.8.", 4, 1, 0, want_dw=param_grads)
+        if callable(dfeat):
+            dfeat(g)
+        elif dfeat is not None:
+            if dfeat.shape != g.shape:
+                raise RuntimeError(f"dfeat: {tuple(g.shape)} expected, got {tuple(dfeat.shape)}")
+            K.axpby(1.0, dfeat, g, True)
         for i in range(2, -1, -1):
             pre, k, s, p, norm = self.CONVS[i]
             a, st, h = tape[i + 1]

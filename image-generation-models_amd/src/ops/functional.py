@@ -1834,17 +1834,18 @@ def bn_seg_bwd(x, mean, rstd, gamma, y, dy, act=None, slope=0.2, dgamma=None, db
     return dx
 
 
-def adv_loss(logit, targets, loss_mode="vanilla", scale=1.0, want_grad=True):
+def adv_loss(logit, targets, loss_mode="vanilla", scale=1.0, want_grad=True, dlogit_out=None):
     """The reference's adversarial_loss (src/utils/losses.py:4-24) per segment of the logits: targets = one bool per segment (True:
     "real").  logit: [N] or a discriminator's NHWC output [N, 1, 1, 1] (a view of a padded buffer: its pitch goes to the kernel).
     Returns (loss[S], mean_logit[S], dlogit) with dlogit = scale * d loss_s / d logit, shaped like logit -- for an NHWC logit a view
     of a zero-padded [N, 1, 1, 4] buffer, what the convolutions' backward reads -- or None.  "hinge" is the reference's formula:
-    max(1 - x, 1) for real targets."""
+    max(1 - x, 1) for real targets.  dlogit_out: N rows of a zero-padded [.., 1, 1, 4] buffer the caller holds, written instead of a new
+    one (the VAE-GAN fills some segments of a longer gradient and leaves the others zero)."""
     _need_gpu(logit)
     mode = ADV_LOSSES.get(loss_mode)
     if mode is None:
         raise NotImplementedError(f"loss_mode={loss_mode!r}: 'vanilla', 'lsgan' or 'hinge'")
-    return _adv_loss(logit, targets, mode, scale, want_grad)
+    return _adv_loss(logit, targets, mode, scale, want_grad, dlogit_out)
 
 
 _WASSERSTEIN = 3        # mi_adv_loss' mode 3; not a `loss_mode` of the GAN, so not in ADV_LOSSES
@@ -1857,7 +1858,7 @@ def critic_loss(logit, targets, scale=1.0, want_grad=True):
     return _adv_loss(logit, targets, _WASSERSTEIN, scale, want_grad)
 
 
-def _adv_loss(logit, targets, mode, scale, want_grad):
+def _adv_loss(logit, targets, mode, scale, want_grad, dlogit_out=None):
     N = logit.shape[0]
     if logit.numel() != N or logit.dtype != torch.float32 or N < 1:
         raise RuntimeError("adv_loss: float32 logits [N] or [N, 1, 1, 1] are expected")
@@ -1867,7 +1868,11 @@ def _adv_loss(logit, targets, mode, scale, want_grad):
         raise RuntimeError(f"adv_loss: {N} logits do not split into {S} equal segments")
     out = torch.empty((2, S), device=logit.device, dtype=torch.float32)
     dlogit, lddl = None, 0
-    if want_grad and logit.dim() == 4:
+    if want_grad and dlogit_out is not None:
+        if not (dlogit_out.is_cuda and dlogit_out.dtype == torch.float32 and dlogit_out.shape == (N, 1, 1, 1) and (N == 1 or dlogit_out.stride(0) == 4)):
+            raise RuntimeError(f"adv_loss: dlogit_out is [{N}, 1, 1, 1] float32, a view of a [.., 1, 1, 4] buffer")
+        dlogit, lddl = dlogit_out, 4
+    elif want_grad and logit.dim() == 4:
         dlogit, lddl = torch.zeros((N, 1, 1, 4), device=logit.device, dtype=torch.float32)[..., :1], 4
     elif want_grad:
         dlogit, lddl = torch.empty(N, device=logit.device, dtype=torch.float32), 1
@@ -2126,6 +2131,111 @@ def age_image_mse(pred_nhwc, target_nchw, want_grad=True, gscale=1.0):
     check(lib.mi_age_image_mse(B, Cc, H * W, _p(pred_nhwc), ld, _p(target_nchw), _p(loss), _p(dpred), float(gscale), _p(ws), _stream()),
           "mi_age_image_mse")
     return loss[0], (dpred[..., :Cc] if want_grad else None)
+
+
+# --------------------------------------------------------------------------- VAE-GAN operators (vaegan_ops.hip)
+def _vg_rows(t, what, cols=None):
+    """t [rows, cols] or a net's NHWC output [rows, 1, 1, cols] (a view of a padded buffer) -> (rows, cols, pitch)."""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise RuntimeError(f"{what}: libmi_ddpm kernels need tensors on an MI355X (HIP) device; there is no CPU fallback")
+    _need_gpu(t)
+    rows, L = t.shape[0], t.shape[-1]
+    if t.dtype != torch.float32 or t.dim() not in (2, 4) or t.numel() != rows * L or (L > 1 and t.stride(-1) != 1) or (cols and L != cols):
+        raise RuntimeError(f"{what}: float32 rows [rows, {cols or 'L'}] or [rows, 1, 1, {cols or 'L'}] with unit column stride are expected")
+    return rows, L, (max(L, t.stride(0)) if rows > 1 else L)
+
+
+def vaegan_latent_fwd(h, eps, prior):
+    """h [N, 2L] = [mu | log_sigma] (or the encoder's NHWC output [N, 1, 1, 2L], read in place), eps [N, L], prior [N, L] ->
+    (zz [2N, 1, 1, L], kld): the decoder's NHWC input for ONE segments=2 pass, rows [0, N) = mu + exp(log_sigma) eps, rows [N, 2N) =
+    prior -- a view of a [2N, 1, 1, 4 ceil(L / 4)] buffer whose padded lanes are 0 -- and the KL term of K.vae_latent_fwd, stored.
+    One launch."""
+    N, L2, ldh = _vg_rows(h, "vaegan_latent_fwd: h")
+    L = L2 // 2
+    if L2 != 2 * L or L < 1:
+        raise RuntimeError("vaegan_latent_fwd: h holds [mu | log_sigma], an even number of columns")
+    for t, what in ((eps, "eps"), (prior, "prior")):
+        _vg_rows(t, f"vaegan_latent_fwd: {what}", L)
+        if t.shape[0] != N or not t.is_contiguous():
+            raise RuntimeError(f"vaegan_latent_fwd: {what} [{N}, {L}], dense, is expected")
+    ldz = (L + 3) // 4 * 4
+    lib = load_library()
+    if lib.mi_vaegan_latent_supported(N, L) != 1:
+        check(-1, "mi_vaegan_latent_supported")
+    zz = torch.empty((2 * N, 1, 1, ldz), device=h.device, dtype=torch.float32)
+    kld = torch.empty((), device=h.device, dtype=torch.float32)
+    check(lib.mi_vaegan_latent_fwd(N, L, _p(h), ldh, _p(eps), _p(prior), _p(zz), ldz, _p(kld), _stream()), "mi_vaegan_latent_fwd")
+    return zz[..., :L], kld
+
+
+def vaegan_latent_bwd(h, eps, dz, g_kld=1.0, dz_scale=1.0):
+    """dh [N, 1, 1, 2L] (a view of a [N, 1, 1, 4 ceil(2L / 4)] buffer whose padded lanes are 0: what ConvEncoder.backward_nhwc takes as
+    dout) from the first N rows of dz (the decoder's input gradient [>= N, L] or [>= N, 1, 1, L], any pitch) times dz_scale, plus
+    g_kld times the KL term's gradient.  One launch."""
+    N, L2, ldh = _vg_rows(h, "vaegan_latent_bwd: h")
+    L = L2 // 2
+    rows, _, lddz = _vg_rows(dz, "vaegan_latent_bwd: dz", L)
+    if rows < N or not (eps.is_cuda and eps.dtype == torch.float32 and eps.shape == (N, L) and eps.is_contiguous()):
+        raise RuntimeError(f"vaegan_latent_bwd: dz with at least {N} rows and a dense float32 eps [{N}, {L}] on the device are expected")
+    lddh = (L2 + 3) // 4 * 4
+    dh = torch.empty((N, 1, 1, lddh), device=h.device, dtype=torch.float32)
+    check(load_library().mi_vaegan_latent_bwd(N, L, _p(h), ldh, _p(eps), _p(dz), lddz, float(dz_scale), float(g_kld), _p(dh), lddh, _stream()),
+          "mi_vaegan_latent_bwd")
+    return dh[..., :L2]
+
+
+def feat_match(real, recon, drecon=None, gscale=1.0, accumulate=False, want_grad=True):
+    """The VAE-GAN's reconstruction loss in discriminator-feature space: (sum (real - recon)^2 / N, its gradient by recon times gscale)
+    for two dense blocks [N, ...] of the same shape (two segments of netD's last hidden NHWC activation, read in place).  drecon: a
+    dense block of that shape to store into, or to add into with accumulate (the recon segment's rows of netD's gradient buffer);
+    None with want_grad allocates one; want_grad=False: the loss alone.  The loss is summed in a fixed order.  Two launches."""
+    _need_gpu(real)
+    N = real.shape[0]
+    per = real[0].numel()
+    if not (real.shape == recon.shape and real.dtype == recon.dtype == torch.float32 and real.is_contiguous() and recon.is_contiguous()):
+        raise RuntimeError("feat_match: two dense float32 blocks of one shape are expected")
+    if not want_grad:
+        drecon = None
+    elif drecon is None:
+        if accumulate:
+            raise RuntimeError("feat_match: accumulate needs the buffer to add into")
+        drecon = torch.empty_like(recon)
+    elif not (drecon.shape == recon.shape and drecon.dtype == torch.float32 and drecon.is_contiguous() and drecon.device == real.device):
+        raise RuntimeError("feat_match: drecon is a dense float32 block shaped like recon")
+    lib = load_library()
+    if lib.mi_feat_match_supported(N, per) != 1:
+        check(-1, "mi_feat_match_supported")
+    loss = torch.empty(1, device=real.device, dtype=torch.float32)
+    ws = torch.empty(lib.mi_feat_match_workspace_doubles(N, per), device=real.device, dtype=torch.float64)
+    check(lib.mi_feat_match(N, per, _p(real), _p(recon), _p(loss), _p(drecon), float(gscale), int(bool(accumulate)), _p(ws), _stream()),
+          "mi_feat_match")
+    return loss[0], drecon
+
+
+def vaegan_pack_fwd(dec_out, imgs):
+    """netD's input for ONE segments=3 pass: [fake | nhwc(imgs) | recon] as [3N, H, W, C] (a view of a buffer with the decoder's pixel
+    pitch, padded lanes 0) from the decoder's [recon | fake] NHWC output [2N, H, W, C] and the NCHW batch [N, C, H, W].  One launch."""
+    _need_gpu(dec_out)
+    N, Cc, H, W = imgs.shape
+    if not (imgs.is_cuda and imgs.dtype == torch.float32 and imgs.is_contiguous() and dec_out.shape == (2 * N, H, W, Cc)):
+        raise RuntimeError("vaegan_pack_fwd: a dense float32 batch [N, C, H, W] on the device and a decoder output [2N, H, W, C] are expected")
+    ld = ld_of(dec_out)
+    x = torch.empty((3 * N, H, W, ld), device=dec_out.device, dtype=torch.float32)
+    check(load_library().mi_vaegan_pack_fwd(N, Cc, H * W, _p(dec_out), _p(imgs), _p(x), ld, _stream()), "mi_vaegan_pack_fwd")
+    return x[..., :Cc]
+
+
+def vaegan_unpack_bwd(dx, s_recon=1.0, s_fake=1.0):
+    """The decoder's upstream gradient [s_recon dx[2N:3N] | s_fake dx[0:N]] as [2N, H, W, C] (padded lanes 0) from netD's input
+    gradient dx [3N, H, W, C] over [fake | real | recon].  One launch."""
+    _need_gpu(dx)
+    N3, H, W, Cc = dx.shape
+    if N3 % 3 != 0 or dx.dtype != torch.float32:
+        raise RuntimeError("vaegan_unpack_bwd: a float32 gradient [3N, H, W, C] is expected")
+    N, ld = N3 // 3, ld_of(dx)
+    dy = torch.empty((2 * N, H, W, ld), device=dx.device, dtype=torch.float32)
+    check(load_library().mi_vaegan_unpack_bwd(N, Cc, H * W, _p(dx), float(s_recon), float(s_fake), _p(dy), ld, _stream()), "mi_vaegan_unpack_bwd")
+    return dy[..., :Cc]
 
 
 # --------------------------------------------------------------------------- WGAN-GP operators (critic_ops.hip)

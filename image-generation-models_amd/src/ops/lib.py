@@ -243,6 +243,11 @@ SIGNATURES = {
     "mi_age_image_mse": [_I, _I, _I, _P, _I, _P, _P, _P, _F, _P, _P],
     "mi_age_moments_fwd": [_I, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
     "mi_age_moments_bwd": [_I, _I, _I, _P, _I, _P, _P, _P, _F, _F, _I, _I, _F, _F, _P, _I, _P, _P, _I, _P, _I, _P],
+    "mi_vaegan_latent_fwd": [_I, _I, _P, _I, _P, _P, _P, _I, _P, _P],
+    "mi_vaegan_latent_bwd": [_I, _I, _P, _I, _P, _P, _I, _F, _F, _P, _I, _P],
+    "mi_feat_match": [_I, _I, _P, _P, _P, _P, _F, _I, _P, _P],
+    "mi_vaegan_pack_fwd": [_I, _I, _I, _P, _P, _P, _I, _P],
+    "mi_vaegan_unpack_bwd": [_I, _I, _I, _P, _F, _F, _P, _I, _P],
     "mi_rmsprop_step": [_Z, _P, _P, _P, _F, _F, _F, _F, _P],
     "mi_clamp_inplace": [_Z, _P, _F, _F, _P],
     "mi_adam_tick": [_P, _P],
@@ -308,6 +313,10 @@ OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_info_head_workspace_doubles": ([_I], C.c_size_t),
          "mi_age_moments_workspace_doubles": ([_I, _I], C.c_size_t),
          "mi_age_image_mse_workspace_doubles": ([_I, _I], C.c_size_t),
+         "mi_feat_match_workspace_doubles": ([_I, _I], C.c_size_t),
+         "mi_vaegan_latent_supported": ([_I, _I], C.c_int),
+         "mi_feat_match_supported": ([_I, _I], C.c_int),
+         "mi_vaegan_pack_supported": ([_I, _I, _I, _I], C.c_int),
          "mi_colsum_ordered_workspace": ([_I, _I], C.c_size_t),
          "mi_conv_wgrad_slabs_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),
          "mi_chan_layernorm_bwd_part_rows": ([_I, _I], C.c_int),

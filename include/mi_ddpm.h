@@ -861,6 +861,35 @@ int mi_age_moments_bwd(int S, int M, int L, const float* z, int ldz, const float
                        float c1, int mode0, int mode1, float w0, float w1, const float* t, int ldt, const float* dz_ext0,
                        const float* dz_ext1, int ldx, float* de, int ldde, void* stream);
 
+/* ---- VAE-GAN operators (reference src/models/vae_gan.py:63-102; csrc/vaegan_ops.hip) ----
+ * fp32 tensors, every sum fp64 in a fixed order and rounded once, no atomics, every element of every output stored (pad lanes as 0),
+ * the workspace needs no zeroing: two runs agree bit for bit.  Output rows have pitches that are multiples of 4 floats and 16-byte
+ * aligned bases: every store is a 16-byte access.  A refused call returns non-zero with mi_last_error() set and writes nothing.
+ * latent_supported: 1 for N >= 1, L >= 1, N (L + 3) < 2^27, else 0 with a message.
+ * latent_fwd: h [N][ldh >= 2L] = [mu | log_sigma], eps [N][L], prior [N][L] (dense) -> z [2N][ldz], ldz = 4 ceil(L / 4): rows [0, N) =
+ *   mu + exp(log_sigma) eps, rows [N, 2N) = prior, lanes from L on 0 -- the decoder's NHWC input for one segments=2 pass.  kld[0] is
+ *   STORED: mean over rows of -0.5 sum(1 + 2 ls - mu^2 - exp(ls)^2), each term as mi_vae_latent_fwd forms it, summed in fp64.  1 launch.
+ * latent_bwd: dh [N][lddh], lddh = 4 ceil(2L / 4): lanes [0, L) = d + gk mu, [L, 2L) = d eps exp(ls) + gk (exp(ls)^2 - 1), the rest 0,
+ *   with d = dz_scale * dz[n][k] (dz: the first N rows of the decoder's input gradient, rows of lddz >= L) and gk = g_kld / N.  1 launch.
+ * feat_match: real, recon: two dense 16-byte aligned blocks of N * per floats (per % 4 == 0; two segments of netD's last hidden NHWC
+ *   activation, read in place).  loss[0] = sum (real - recon)^2 / N, stored.  drecon (nullable, may be a segment of a larger buffer) =
+ *   gscale * 2 (recon - real) / N, stored (accumulate == 0) or added.  ws: mi_feat_match_workspace_doubles(N, per) doubles.  2 launches.
+ * pack_fwd: dec_out [2N][HW][ld] = the decoder's [recon | fake] output and the NCHW batch -> x [3N][HW][ld] = [fake | nhwc(imgs) | recon],
+ *   ld % 4 == 0, ld >= C, lanes from C on 0.  unpack_bwd: dx [3N][HW][ld] (netD's input gradient) -> dy [2N][HW][ld] =
+ *   [s_recon dx[2N:3N] | s_fake dx[0:N]], lanes from C on 0.  1 launch each; 3 N HW ld < 2^31. */
+int mi_vaegan_latent_supported(int N, int L);
+int mi_vaegan_latent_fwd(int N, int L, const float* h, int ldh, const float* eps, const float* prior, float* z, int ldz, float* kld,
+                         void* stream);
+int mi_vaegan_latent_bwd(int N, int L, const float* h, int ldh, const float* eps, const float* dz, int lddz, float dz_scale, float g_kld,
+                         float* dh, int lddh, void* stream);
+int mi_feat_match_supported(int N, int per);
+size_t mi_feat_match_workspace_doubles(int N, int per);
+int mi_feat_match(int N, int per, const float* real, const float* recon, float* loss, float* drecon, float gscale, int accumulate,
+                  double* ws, void* stream);
+int mi_vaegan_pack_supported(int N, int C, int HW, int ld);
+int mi_vaegan_pack_fwd(int N, int C, int HW, const float* dec_out, const float* imgs_nchw, float* x, int ld, void* stream);
+int mi_vaegan_unpack_bwd(int N, int C, int HW, const float* dx, float s_recon, float s_fake, float* dy, int ld, void* stream);
+
 /* ---- small element-wise pieces ---------------------------------------------------------------- */
 /* SinusoidalPosEmb (ddpm.py:52-59): out[b][dim] = [sin(t f_j) | cos(t f_j)] */
 int mi_time_embed(int B, int dim, const int64_t* t, float* out, void* stream);
