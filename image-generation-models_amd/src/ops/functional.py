@@ -4,11 +4,15 @@ Activations are fp32 NHWC tensors [N, H, W, C] on a HIP device; a channel slice
 ``t[..., a:b]`` of a contiguous tensor is a legal activation (pixel stride ld = t.stride(2)).
 Every function launches on torch's current stream and never synchronises.  There is no
 CPU path: a tensor that is not on a GPU raises.
+
+Shape questions (`*_supported`, `*_tile`, `*_picked`, workspace sizes) are answered once per shape and kept in _QUERY_CACHE, the only
+cache here: a library query goes through `_query`, Python logic around queries carries `@_cached_question`.  Their arguments are
+numbers and tuples of numbers; a launch wrapper is never cached.  `_QUERY_CACHE.clear()` follows any debug hook of the library and
+any rebinding of a module switch (PW_MIN_TILES, USE_*) that an answer depends on.
 """
 from __future__ import annotations
 
 import ctypes as C
-import functools
 import os
 from typing import Optional, Tuple
 
@@ -71,30 +75,66 @@ PW_MIN_TILES = int(debug_knob("MI_CONV_PW_MIN_TILES", "64"))
 USE_WGRAD_TR = debug_knob("MI_W3_TR", "1") != "0"      # A/B switch for the LDS-DMA weight-gradient kernel (csrc/wgrad_tr.hip)
 
 
-_QUERY_CACHE = {}
+_QUERY_CACHE, _MISSING = {}, object()
 
 
 def _desc_key(d):
     return tuple(getattr(d, f) for f, _ in d._fields_)
 
 
-def _query(name, d, *extra):
-    """Cached yes / no (or size) answer of a descriptor query of the library: the answers are pure functions of the descriptor, and
-    one FFI call per launch for them was ~15 % of the step's enqueue time."""
-    key = (name, _desc_key(d)) + extra
-    r = _QUERY_CACHE.get(key)
-    if r is None:
-        r = getattr(load_library(), name)(C.byref(d), *extra)
-        _QUERY_CACHE[key] = r
+def _query(name, *args):
+    """Cached answer (yes / no, tile, size) of a library query, keyed by its arguments' values (a descriptor: its fields).  The answers
+    are pure functions of them, and one FFI call per launch for them was ~15 % of the step's enqueue time."""
+    key = (name, *[_desc_key(a) if isinstance(a, C.Structure) else a for a in args])
+    r = _QUERY_CACHE.get(key, _MISSING)
+    if r is _MISSING:
+        r = _QUERY_CACHE[key] = getattr(load_library(), name)(*[C.byref(a) if isinstance(a, C.Structure) else a for a in args])
     return r
 
 
-@functools.lru_cache(maxsize=None)
+def _cached_question(fn):
+    """A shape question written in Python: evaluated once per (name, positional, sorted keyword arguments), kept in _QUERY_CACHE.
+    A tensor among the arguments is a TypeError: what takes tensors launches, and a launch is never answered from a cache."""
+    name = fn.__name__
+
+    def ask(*args, **kw):
+        key = (name, args, tuple(sorted(kw.items()))) if kw else (name, args)
+        r = _QUERY_CACHE.get(key, _MISSING)
+        if r is _MISSING:
+            if any(isinstance(x, torch.Tensor) for a in (*args, *kw.values()) for x in (a if isinstance(a, tuple) else (a,))):
+                raise TypeError(f"{name}: a cached shape question takes numbers and tuples of numbers, not tensors")
+            r = _QUERY_CACHE[key] = fn(*args, **kw)
+        return r
+    ask.__name__, ask.__qualname__, ask.__doc__, ask.__wrapped__ = name, fn.__qualname__, fn.__doc__, fn
+    return ask
+
+
+def _conv_desc(N, H, W, K, Nc, k, *, out_hw=None, stride=1, pad=None, transposed=False, w_kn=False, mode=MODE_BF16, K1=None, ldx=None,
+               ldx2=0, ldy=None, ldr=0, accumulate=False):
+    """MiConvDesc of a k x k (or k = (kh, kw)) conv on an H x W input.  Unless told otherwise: stride 1, pad k // 2, output of the same
+    size, bf16 mode, one dense source (K1 = ldx = K, ldx2 = 0), dense output (ldy = Nc), no residual, no accumulate."""
+    OH, OW = (H, W) if out_hw is None else out_hw
+    kh, kw = k if isinstance(k, tuple) else (k, k)
+    return MiConvDesc(N, H, W, OH, OW, K, Nc, kh, kw, stride, kh // 2 if pad is None else pad, int(transposed), int(w_kn), mode,
+                      K if K1 is None else K1, K if ldx is None else ldx, ldx2, Nc if ldy is None else ldy, ldr, int(accumulate))
+
+
+def _wgrad_desc(N, grid_g, grid_d, Ci, Cj, k, stride, pad, gather_i, mode, ldp, ldq, I1=None, ldp2=0):
+    """MiWgradDesc: the gathered operand on grid_g = (H, W), the other on grid_d; k x k (or k = (kh, kw)); P in one piece unless I1, ldp2."""
+    kh, kw = k if isinstance(k, tuple) else (k, k)
+    return MiWgradDesc(N, grid_g[0], grid_g[1], grid_d[0], grid_d[1], Ci, Cj, kh, kw, stride, pad, int(gather_i), mode, Ci if I1 is None else I1, ldp, ldp2, ldq)
+
+
+def _ldn(t) -> int:
+    return 0 if t is None else ld_of(t)
+
+
+@_cached_question
 def _linattn_ws(N, n, heads):
     return load_library().mi_linattn_workspace(N, n, heads)
 
 
-@functools.lru_cache(maxsize=None)
+@_cached_question
 def _cvt_colsum_ws(M, Cc):
     return load_library().mi_f32_to_bf16_colsum_workspace(M, Cc)
 
@@ -191,12 +231,10 @@ def _b16(t) -> int:
 
 
 # --------------------------------------------------------------------------- conv family
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def igemm_bf16_in_supported(K, Nc, k, stride, transposed, mode, out_hw):
     """Can conv_igemm read bf16-stored activations for this layer (the stride-2 conv / transposed conv family, dense tensors)?"""
-    d = MiConvDesc(N=1, IH=1, IW=1, OH=out_hw[0], OW=out_hw[1], K=K, Nc=Nc, KH=k, KW=k, stride=stride, pad=1, transposed=int(transposed),
-                   w_kn=0, mode=mode, K1=K, ldx=K, ldx2=0, ldy=Nc, ldr=0, accumulate=0)
-    return bool(load_library().mi_conv_igemm_bf16w_io_supported(C.byref(d)))
+    return bool(_query("mi_conv_igemm_bf16w_io_supported", _conv_desc(1, 1, 1, K, Nc, k, out_hw=out_hw, stride=stride, pad=1, transposed=transposed, mode=mode)))
 
 
 USE_CONV_GT = debug_knob("MI_CONV_GT", "1") != "0"      # A/B switch: the tap-gather kernel for the stride-2 / transposed convs
@@ -212,9 +250,8 @@ def conv_gt(x, wq, *, kh, kw, stride, pad, transposed, K, Nc, out_hw, bias=None,
     _need_gpu(x)
     N, IH, IW, _ = x.shape
     OH, OW = out_hw
-    d = MiConvDesc(N=N, IH=IH, IW=IW, OH=OH, OW=OW, K=K, Nc=Nc, KH=kh, KW=kw, stride=stride, pad=pad, transposed=int(transposed), w_kn=0,
-                   mode=mode, K1=K, ldx=ld_of(x), ldx2=0, ldy=Nc if out is None else ld_of(out),
-                   ldr=ld_of(residual) if residual is not None else 0, accumulate=int(accumulate))
+    d = _conv_desc(N, IH, IW, K, Nc, (kh, kw), out_hw=out_hw, stride=stride, pad=pad, transposed=transposed, mode=mode, ldx=ld_of(x),
+                   ldy=Nc if out is None else ld_of(out), ldr=_ldn(residual), accumulate=accumulate)
     if d.ldy % 8 or not _query("mi_conv_gt_supported", d):
         return None
     if out is None:
@@ -254,10 +291,8 @@ def conv_igemm(x, w, *, kh, kw, stride, pad, transposed, w_kn, K, Nc, out_hw, mo
         if out.shape[3] != Nc:
             out.zero_()
             out = out[..., :Nc]
-    d = MiConvDesc(N=N, IH=IH, IW=IW, OH=OH, OW=OW, K=K, Nc=Nc, KH=kh, KW=kw, stride=stride, pad=pad,
-                   transposed=int(transposed), w_kn=int(w_kn), mode=mode, K1=K1, ldx=ld_of(x),
-                   ldx2=ld_of(x2) if x2 is not None else 0, ldy=ld_of(out),
-                   ldr=ld_of(residual) if residual is not None else 0, accumulate=int(accumulate))
+    d = _conv_desc(N, IH, IW, K, Nc, (kh, kw), out_hw=out_hw, stride=stride, pad=pad, transposed=transposed, w_kn=w_kn, mode=mode, K1=K1,
+                   ldx=ld_of(x), ldx2=_ldn(x2), ldy=ld_of(out), ldr=_ldn(residual), accumulate=accumulate)
     if PROBE is not None:
         bm, bn = C.c_int(), C.c_int()
         load_library().mi_conv_igemm_tile(C.byref(d), C.byref(bm), C.byref(bn))
@@ -294,9 +329,7 @@ def conv3x3_bf16w(x, wsh, *, K, Nc, flip, ksize=3, x2=None, bias=None, residual=
     N, H, W, K1 = x.shape
     if x2 is None:
         K1 = K
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=ksize, KW=ksize, stride=1, pad=ksize // 2, transposed=int(flip),
-                   w_kn=0, mode=MODE_BF16, K1=K1, ldx=ld_of(x), ldx2=ld_of(x2) if x2 is not None else 0, ldy=0,
-                   ldr=ld_of(residual) if residual is not None else 0, accumulate=int(accumulate))
+    d = _conv_desc(N, H, W, K, Nc, ksize, transposed=flip, K1=K1, ldx=ld_of(x), ldx2=_ldn(x2), ldy=0, ldr=_ldn(residual), accumulate=accumulate)
     lib = load_library()
     if not _query("mi_conv3x3_bf16w_supported", d):
         return None
@@ -474,18 +507,15 @@ def gn_mish_apply_sums(x, sums, gamma, beta, *, groups=8, eps=1e-5, temb=None, r
     return (y, stats, y16) if want16 else (y, stats)
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def conv3x3_gn_mish_supported(N, H, W, K, Nc):
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=0, w_kn=0, mode=MODE_BF16, K1=K,
-                   ldx=K, ldx2=K, ldy=Nc, ldr=0, accumulate=0)
-    return bool(load_library().mi_conv3x3_gn_mish_supported(C.byref(d)))
+    return bool(_query("mi_conv3x3_gn_mish_supported", _conv_desc(N, H, W, K, Nc, 3, ldx2=K)))
 
 
-@functools.lru_cache(maxsize=None)
+@_cached_question
 def conv3x3_pw_gn_mish_picked(N, H, W, K, Nc):
     """Does conv3x3_gn_mish route a bf16-stored layer of this shape to the private-weight-stream fused kernel (given wq)?"""
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=0, w_kn=0, mode=MODE_BF16, K1=K,
-                   ldx=K, ldx2=K, ldy=Nc, ldr=0, accumulate=0)
+    d = _conv_desc(N, H, W, K, Nc, 3, ldx2=K)
     # Where it pays (measured in the B = 64 sampler, round 4): every 64-channel chunk of K costs the fused kernel one transform block
     # (~1 us that the matrix pipe of that workgroup waits for), the GroupNorm pass it replaces costs ~4 us + its bytes -- the fusion
     # wins up to K = 256 (level 0: -2.3 us per block, 256 channels @16x16: -4 us) and loses on the 512-channel 8x8 layers (+2 us)
@@ -507,8 +537,7 @@ def conv3x3_gn_mish(x, coef, wsh, *, K, Nc, bias=None, out_dtype=None, gn=None, 
     the kernel.  Returns None when the shape is not supported."""
     _need_gpu(x)
     N, H, W, _ = x.shape
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=0, w_kn=0, mode=MODE_BF16, K1=K,
-                   ldx=ld_of(x), ldx2=ld_of(x), ldy=Nc, ldr=0, accumulate=0)
+    d = _conv_desc(N, H, W, K, Nc, 3, ldx=ld_of(x), ldx2=ld_of(x))
     lib = load_library()
     ptf = _pick_pw_fused(N, H, W, Nc, d, x.dtype == torch.float32) if (wq is not None and USE_CONV_PW) else 0
     if ptf and x.dtype == torch.bfloat16:
@@ -621,9 +650,7 @@ def conv3x3_f32(x, wq32, *, K, Nc, flip, x2=None, bias=None, residual=None, out=
     N, H, W, K1 = x.shape
     if x2 is None:
         K1 = K
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=int(flip),
-                   w_kn=0, mode=MODE_FP32, K1=K1, ldx=ld_of(x), ldx2=ld_of(x2) if x2 is not None else 0, ldy=Nc,
-                   ldr=ld_of(residual) if residual is not None else 0, accumulate=int(accumulate))
+    d = _conv_desc(N, H, W, K, Nc, 3, transposed=flip, mode=MODE_FP32, K1=K1, ldx=ld_of(x), ldx2=_ldn(x2), ldr=_ldn(residual), accumulate=accumulate)
     pt = _query("mi_conv3x3_pw_f32_tile", d)
     if not pt:
         return None
@@ -651,9 +678,7 @@ def conv1x1_f32(x, wq32, *, K, Nc, flip, x2=None, bias=None, residual=None, out=
     N, H, W, K1 = x.shape
     if x2 is None:
         K1 = K
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=1, KW=1, stride=1, pad=0, transposed=int(flip),
-                   w_kn=0, mode=MODE_FP32, K1=K1, ldx=ld_of(x), ldx2=ld_of(x2) if x2 is not None else 0, ldy=Nc,
-                   ldr=ld_of(residual) if residual is not None else 0, accumulate=int(accumulate))
+    d = _conv_desc(N, H, W, K, Nc, 1, transposed=flip, mode=MODE_FP32, K1=K1, ldx=ld_of(x), ldx2=_ldn(x2), ldr=_ldn(residual), accumulate=accumulate)
     if not _query("mi_conv1x1_pw_f32_supported", d):
         return None
     if out is None:
@@ -672,7 +697,7 @@ def conv1x1_f32(x, wq32, *, K, Nc, flip, x2=None, bias=None, residual=None, out=
     return out
 
 
-@functools.lru_cache(maxsize=None)
+@_cached_question
 def small_cin_supported(ks, Cin, Cout, wgrad=False):
     """The 3-channel-input kernels (mi_conv_small_cin_*): which (kernel size, Cin, Cout) they take."""
     if ks not in (1, 3) or not 1 <= Cin <= 4:
@@ -682,7 +707,7 @@ def small_cin_supported(ks, Cin, Cout, wgrad=False):
     return Cout >= 4 and Cout % 4 == 0 and Cout <= 1024 and 256 % (Cout // 4) == 0
 
 
-@functools.lru_cache(maxsize=None)
+@_cached_question
 def small_cin_bf16_supported(ks, N, H, W, Cin, Cout, ldx):
     """The first Block's conv (Cin <= 4) can write its output as bf16 AND its weight gradient can read a bf16 dy (round 4)."""
     return bool(load_library().mi_conv_small_cin_bf16_supported(ks, N, H, W, Cin, Cout, ldx))
@@ -712,7 +737,7 @@ def conv1x1_small_cout_bwd(x, dy, w, dW, dx, accumulate=False):
                                         int(accumulate), _p(ws), need, _stream()), "mi_conv1x1_small_cout_bwd")
 
 
-@functools.lru_cache(maxsize=None)
+@_cached_question
 def small_cout_gn_supported(C, Cs, G):
     return bool(load_library().mi_conv1x1_small_cout_gn_supported(C, Cs, G))
 
@@ -733,7 +758,7 @@ def conv1x1_small_cout_gn(x, sums, gamma, beta, w, bias, Cs, groups=8, eps=1e-5)
     return y[..., :Cs]
 
 
-@functools.lru_cache(maxsize=None)
+@_cached_question
 def small_cin_dual_supported(N, H, W, Cin, Cout, ldx):
     return bool(load_library().mi_conv_small_cin_fwd_dual_supported(N, H, W, Cin, Cout, ldx))
 
@@ -774,7 +799,7 @@ def conv_small_cin_wgrad(x, dy, dW, ks):
                                          _stream()), "mi_conv_small_cin_wgrad")
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def small_cout_supported(op, C, Cs):
     """Conv2d(C, Cs<=4, 1) kernels (mi_conv1x1_small_cout): op 0 forward, 1 dgrad, 2 wgrad."""
     if not 1 <= Cs <= 4 or C not in (32, 64, 128, 256):
@@ -813,10 +838,8 @@ def conv_wgrad(P, Q, dW, *, kh, kw, stride, pad, gather_i, Ci, Cj, grid_g, grid_
     in a fixed order, no atomics: two runs give the same bits (fp32 operands)."""
     _need_gpu(P)
     N = P.shape[0]
-    I1 = P.shape[3] if P2 is not None else Ci
-    d = MiWgradDesc(N=N, GH=grid_g[0], GW=grid_g[1], DH=grid_d[0], DW=grid_d[1], Ci=Ci, Cj=Cj, KH=kh, KW=kw,
-                    stride=stride, pad=pad, gather_i=int(gather_i), mode=mode, I1=I1, ldp=ld_of(P),
-                    ldp2=ld_of(P2) if P2 is not None else 0, ldq=ld_of(Q))
+    d = _wgrad_desc(N, grid_g, grid_d, Ci, Cj, (kh, kw), stride, pad, gather_i, mode, ld_of(P), ld_of(Q),
+                    I1=P.shape[3] if P2 is not None else Ci, ldp2=_ldn(P2))
     lib = load_library()
     if ordered:
         if _b16(P) or _b16(Q):
@@ -894,7 +917,6 @@ def conv_wgrad(P, Q, dW, *, kh, kw, stride, pad, gather_i, Ci, Cj, grid_g, grid_
             colsum(Q, dbias)
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
 def conv_s2_wgrad_f32(P, Q, dW, *, k, Ci, Cj, gather_i, grid_g, grid_d):
     """Exact-fp32 mode: the weight gradient of Downsample (3x3 / stride 2, gather_i: P is the big tensor) or Upsample (ConvTranspose 4x4 /
     stride 2: Q is) as k x k gathered problems of the fp32 1x1 weight-gradient kernel (mi_conv_s2_wgrad_f32).  dW [k][k][Ci][Cj] +=.
@@ -903,8 +925,7 @@ def conv_s2_wgrad_f32(P, Q, dW, *, k, Ci, Cj, gather_i, grid_g, grid_d):
         return False
     _need_gpu(P)
     N = P.shape[0]
-    d = MiWgradDesc(N=N, GH=grid_g[0], GW=grid_g[1], DH=grid_d[0], DW=grid_d[1], Ci=Ci, Cj=Cj, KH=k, KW=k, stride=2, pad=1,
-                    gather_i=int(gather_i), mode=MODE_FP32, I1=Ci, ldp=ld_of(P), ldp2=0, ldq=ld_of(Q))
+    d = _wgrad_desc(N, grid_g, grid_d, Ci, Cj, k, 2, 1, gather_i, MODE_FP32, ld_of(P), ld_of(Q))
     if not _query("mi_conv_s2_wgrad_f32_supported", d):
         return False
     lib = load_library()
@@ -918,21 +939,18 @@ def conv_s2_wgrad_f32(P, Q, dW, *, k, Ci, Cj, gather_i, grid_g, grid_d):
     return True
 
 
+@_cached_question
 def s2_wgrad_supported(N, k, Ci, Cj, transposed, big, small, mode):
     """Can the stride-2 LDS-DMA weight-gradient kernel take this Downsample (3x3 conv) / Upsample (4x4 transposed conv) layer
     (dense bf16 operands)?  big / small: the (H, W) of the 2x-resolution tensor and of the other one."""
-    d = MiWgradDesc(N=N, GH=big[0], GW=big[1], DH=small[0], DW=small[1], Ci=Ci, Cj=Cj, KH=k, KW=k, stride=2, pad=1,
-                    gather_i=int(not transposed), mode=mode, I1=Ci, ldp=Ci, ldp2=0, ldq=Cj)
-    return bool(USE_WGRAD_TR and load_library().mi_conv_s2_wgrad_tr_supported(C.byref(d)))
+    return bool(USE_WGRAD_TR and _query("mi_conv_s2_wgrad_tr_supported", _wgrad_desc(N, big, small, Ci, Cj, k, 2, 1, not transposed, mode, Ci, Cj)))
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def conv_gt_supported(N, IH, IW, K, Nc, k, transposed):
     """Does the tap-gather kernel take the Downsample (k = 3) / Upsample (k = 4, transposed) forward conv on a dense bf16 input?"""
-    OH, OW = (2 * IH, 2 * IW) if transposed else ((IH + 2 - k) // 2 + 1, (IW + 2 - k) // 2 + 1)
-    d = MiConvDesc(N=N, IH=IH, IW=IW, OH=OH, OW=OW, K=K, Nc=Nc, KH=k, KW=k, stride=2, pad=1, transposed=int(transposed), w_kn=0,
-                   mode=MODE_BF16, K1=K, ldx=K, ldx2=0, ldy=Nc, ldr=0, accumulate=0)
-    return bool(USE_CONV_GT and Nc % 8 == 0 and load_library().mi_conv_gt_supported(C.byref(d)))
+    out_hw = (2 * IH, 2 * IW) if transposed else ((IH + 2 - k) // 2 + 1, (IW + 2 - k) // 2 + 1)
+    return bool(USE_CONV_GT and Nc % 8 == 0 and _query("mi_conv_gt_supported", _conv_desc(N, IH, IW, K, Nc, k, out_hw=out_hw, stride=2, pad=1, transposed=transposed)))
 
 
 class WgradQueue:
@@ -963,9 +981,8 @@ class WgradQueue:
         return min(pending) - 1 if pending else self.pushed
 
     def _desc(self, P, Q, k, Ci, Cj, hw, mode, P2):
-        I1 = P.shape[3] if P2 is not None else Ci
-        return MiWgradDesc(N=P.shape[0], GH=hw[0], GW=hw[1], DH=hw[0], DW=hw[1], Ci=Ci, Cj=Cj, KH=k, KW=k, stride=1, pad=k // 2, gather_i=1,
-                           mode=mode, I1=I1, ldp=ld_of(P), ldp2=ld_of(P2) if P2 is not None else 0, ldq=ld_of(Q))
+        return _wgrad_desc(P.shape[0], hw, hw, Ci, Cj, k, 1, k // 2, True, mode, ld_of(P), ld_of(Q),
+                           I1=P.shape[3] if P2 is not None else Ci, ldp2=_ldn(P2))
 
     def push(self, P, Q, dW, *, Ci, Cj, hw, mode, P2=None, prefill=False):
         """3x3 / stride 1 / pad 1.  prefill: dW holds no zeros yet (store mode) -- filled here if the layer takes the fallback"""
@@ -1009,8 +1026,7 @@ class WgradQueue:
         """Downsample (3x3 / stride 2 / pad 1 conv: gather_i, P = X on the 2x grid) and Upsample (4x4 / stride 2 / pad 1 transposed
         conv: not gather_i, Q = dY on the 2x grid) weight gradients; both operands bf16.  Returns False when the LDS-DMA kernel
         cannot take the layer (the caller then runs conv_wgrad)."""
-        d = MiWgradDesc(N=P.shape[0], GH=grid_g[0], GW=grid_g[1], DH=grid_d[0], DW=grid_d[1], Ci=Ci, Cj=Cj, KH=k, KW=k, stride=2, pad=1,
-                        gather_i=int(gather_i), mode=mode, I1=Ci, ldp=ld_of(P), ldp2=0, ldq=ld_of(Q))
+        d = _wgrad_desc(P.shape[0], grid_g, grid_d, Ci, Cj, k, 2, 1, gather_i, mode, ld_of(P), ld_of(Q))
         if not (USE_WGRAD_TR and _b16(P) and _b16(Q) and _query("mi_conv_s2_wgrad_tr_supported", d)):
             return False
         self.items2.append((d, P, None, Q, dW))
@@ -1231,8 +1247,7 @@ def gn_mish_fwd(x, gamma, beta, *, groups=8, eps=1e-5, temb=None, residual=None,
     if want16:
         y16 = new_act(N, H, W, Cc, x, torch.bfloat16)
         stats = torch.empty((N, groups, 2), device=x.device, dtype=torch.float32)
-        d = MiGnDesc(N=N, HW=H * W, C=Cc, G=groups, eps=eps, ldx=ld_of(x), ldy=ld_of(y),
-                     ldr=ld_of(residual) if residual is not None else 0)
+        d = MiGnDesc(N=N, HW=H * W, C=Cc, G=groups, eps=eps, ldx=ld_of(x), ldy=ld_of(y), ldr=_ldn(residual))
         io = _b16(x) | (_b16(y) << 1)
         e0 = _probe_open()
         check(load_library().mi_gn_mish_fwd_dual(C.byref(d), _p(x), _p(gamma), _p(beta), _p(temb), ld_of(temb) if temb is not None else 0,
@@ -1242,8 +1257,7 @@ def gn_mish_fwd(x, gamma, beta, *, groups=8, eps=1e-5, temb=None, residual=None,
                          N * H * W * Cc * (_esz(x) + _esz(y) + _esz(residual) + 2))
         return y, stats, y16
     stats = torch.empty((N, groups, 2), device=x.device, dtype=torch.float32)
-    d = MiGnDesc(N=N, HW=H * W, C=Cc, G=groups, eps=eps, ldx=ld_of(x), ldy=ld_of(y),
-                 ldr=ld_of(residual) if residual is not None else 0)
+    d = MiGnDesc(N=N, HW=H * W, C=Cc, G=groups, eps=eps, ldx=ld_of(x), ldy=ld_of(y), ldr=_ldn(residual))
     io = _b16(x) | (_b16(y) << 1)
     ldt = ld_of(temb) if temb is not None else 0
     e0 = _probe_open()
@@ -1294,9 +1308,7 @@ def chan_layernorm_fwd(x, g, b, eps=1e-5, out_dtype=torch.float32):
 
 def ln_conv1x1_supported(N, H, W, K, Nc, ldx=None):
     """Does the LayerNorm + 1x1 conv kernel (mi_ln_conv1x1_pw) take the layer?"""
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=1, KW=1, stride=1, pad=0, transposed=0, w_kn=0, mode=MODE_BF16, K1=K,
-                   ldx=K if ldx is None else ldx, ldx2=0, ldy=Nc, ldr=0, accumulate=0)
-    return bool(_query("mi_ln_conv1x1_pw_supported", d))
+    return bool(_query("mi_ln_conv1x1_pw_supported", _conv_desc(N, H, W, K, Nc, 1, ldx=ldx)))
 
 
 def ln_conv1x1(x, g, b, wq, *, Nc, eps=1e-5, bias=None, want_ln=False):
@@ -1308,8 +1320,7 @@ def ln_conv1x1(x, g, b, wq, *, Nc, eps=1e-5, bias=None, want_ln=False):
     N, H, W, K = x.shape
     y = new_act(N, H, W, Nc, x, torch.bfloat16)
     ln = new_act(N, H, W, K, x, torch.bfloat16) if want_ln else None
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=1, KW=1, stride=1, pad=0, transposed=0, w_kn=0, mode=MODE_BF16, K1=K,
-                   ldx=ld_of(x), ldx2=0, ldy=ld_of(y), ldr=0, accumulate=0)
+    d = _conv_desc(N, H, W, K, Nc, 1, ldx=ld_of(x), ldy=ld_of(y))
     e0 = _probe_open()
     if want_ln:
         check(load_library().mi_ln_conv1x1_pw_dual(C.byref(d), _p(x), _p(g), _p(b), eps, _p(wq), _p(bias), _p(y), _p(ln), ld_of(ln), _stream()),
@@ -1451,8 +1462,7 @@ def linattn_to_out_folded(qkv, w_out16, Cc, bias, residual, heads=4, want16=Fals
                      N * H * W * 2 * hid * 2 + N * Cc * hid * 2)
     y = new_act(N, H, W, Cc, qkv, torch.float32)
     y16 = new_act(N, H, W, Cc, qkv, torch.bfloat16) if want16 else None
-    d = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=hid, Nc=Cc, KH=1, KW=1, stride=1, pad=0, transposed=0, w_kn=0, mode=MODE_BF16, K1=hid,
-                   ldx=C3, ldx2=0, ldy=ld_of(y), ldr=ld_of(residual) if residual is not None else 0, accumulate=0)
+    d = _conv_desc(N, H, W, hid, Cc, 1, ldx=C3, ldy=ld_of(y), ldr=_ldn(residual))
     e0 = _probe_open()
     check(lib.mi_conv1x1_pw_batched(C.byref(d), _p(qkv), _p(weff), Cc * hid, _p(bias), _p(residual), _p(y), 0, _p(y16),
                                     ld_of(y16) if y16 is not None else 0, _stream()), "mi_conv1x1_pw_batched")
@@ -2467,47 +2477,36 @@ def u8_gather_normalize(data_u8, idx, flip=None, normalize=True):
     return out
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def fast3x3_supported(N, H, W, K, Nc, K1=None):
     """(conv via the LDS-tile kernel?, wgrad via the image-major kernel?) for a 3x3/s1/p1 layer in bf16 mode."""
     lib = load_library()
-    dc = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=0, w_kn=0,
-                    mode=MODE_BF16, K1=K1 or K, ldx=4, ldx2=4, ldy=Nc, ldr=0, accumulate=0)
-    dw = MiWgradDesc(N=N, GH=H, GW=W, DH=H, DW=W, Ci=K, Cj=Nc, KH=3, KW=3, stride=1, pad=1, gather_i=1, mode=MODE_BF16,
-                     I1=K1 or K, ldp=4, ldp2=4, ldq=4)
+    dc = _conv_desc(N, H, W, K, Nc, 3, K1=K1 or K, ldx=4, ldx2=4)
+    dw = _wgrad_desc(N, (H, W), (H, W), K, Nc, 3, 1, 1, True, MODE_BF16, 4, 4, I1=K1 or K, ldp2=4)
     return bool(lib.mi_conv3x3_bf16w_supported(C.byref(dc))), bool(lib.mi_conv3x3_wgrad_supported(C.byref(dw)))
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def fast1x1_supported(N, H, W, K, Nc):
     """(conv + dgrad via the LDS-tile kernel?, wgrad via the image-major kernel?) for a 1x1 layer in bf16 mode."""
     lib = load_library()
-    ok = True
-    for k, n in ((K, Nc), (Nc, K)):             # forward and data gradient
-        dc = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=k, Nc=n, KH=1, KW=1, stride=1, pad=0, transposed=0, w_kn=0,
-                        mode=MODE_BF16, K1=k, ldx=8, ldx2=8, ldy=n, ldr=0, accumulate=0)
-        ok = ok and bool(lib.mi_conv3x3_bf16w_supported(C.byref(dc)))
-    dw = MiWgradDesc(N=N, GH=H, GW=W, DH=H, DW=W, Ci=K, Cj=Nc, KH=1, KW=1, stride=1, pad=0, gather_i=1, mode=MODE_BF16,
-                     I1=K, ldp=8, ldp2=8, ldq=8)
+    ok = all(lib.mi_conv3x3_bf16w_supported(C.byref(_conv_desc(N, H, W, k, n, 1, ldx=8, ldx2=8))) for k, n in ((K, Nc), (Nc, K)))   # forward, dgrad
+    dw = _wgrad_desc(N, (H, W), (H, W), K, Nc, 1, 1, 0, True, MODE_BF16, 8, 8, ldp2=8)
     return ok, bool(lib.mi_conv3x3_wgrad_supported(C.byref(dw)))
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def conv1x1_tile_supported(N, H, W, K, Nc, K1=None):
     """Does the 1x1 tile kernel take the forward conv over dense bf16 input(s) -- K1 < K: the skip concat's two sources, K1 and K - K1
     channels (res_conv of the up path)?  conv3x3_bf16w(ksize=1) then returns a tensor."""
     k1 = K1 or K
-    dc = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=1, KW=1, stride=1, pad=0, transposed=0, w_kn=0,
-                    mode=MODE_BF16, K1=k1, ldx=k1, ldx2=(K - k1) if k1 < K else 0, ldy=Nc, ldr=0, accumulate=0)
-    return bool(load_library().mi_conv3x3_bf16w_supported(C.byref(dc)))
+    return bool(_query("mi_conv3x3_bf16w_supported", _conv_desc(N, H, W, K, Nc, 1, K1=k1, ldx=k1, ldx2=(K - k1) if k1 < K else 0)))
 
 
-@functools.lru_cache(maxsize=None)      # pure function of the shape: one FFI query per distinct layer, not per step
+@_cached_question
 def conv3x3_uses_splitk(N, H, W, K, Nc, K1=None):
     """Would the 3x3 LDS-tile kernel run this layer with the split-K plan (fp32 output only)?"""
-    dc = MiConvDesc(N=N, IH=H, IW=W, OH=H, OW=W, K=K, Nc=Nc, KH=3, KW=3, stride=1, pad=1, transposed=0, w_kn=0,
-                    mode=MODE_BF16, K1=K1 or K, ldx=4, ldx2=4, ldy=Nc, ldr=0, accumulate=0)
-    return bool(load_library().mi_conv3x3_bf16w_uses_splitk(C.byref(dc)))
+    return bool(_query("mi_conv3x3_bf16w_uses_splitk", _conv_desc(N, H, W, K, Nc, 3, K1=K1 or K, ldx=4, ldx2=4)))
 
 
 # ---------------------------------------------------------------------------------------------------------- PixelCNN (csrc/pixelcnn.hip)

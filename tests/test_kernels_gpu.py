@@ -2275,3 +2275,32 @@ def test_stride2_wgrad_exact_fp32_gathered_taps(K):
     assert not K.conv_s2_wgrad_f32(z(2, 16, 64, torch.bfloat16), z(2, 8, 64), torch.zeros(9 * 64 * 64, device=DEV), k=3, Ci=64, Cj=64, gather_i=True, grid_g=(16, 16), grid_d=(8, 8))
     assert not K.conv_s2_wgrad_f32(z(2, 12, 64), z(2, 6, 64), torch.zeros(9 * 64 * 64, device=DEV), k=3, Ci=64, Cj=64, gather_i=True, grid_g=(12, 12), grid_d=(6, 6))
     assert not K.conv_s2_wgrad_f32(z(2, 16, 32), z(2, 8, 64), torch.zeros(9 * 32 * 64, device=DEV), k=3, Ci=32, Cj=64, gather_i=True, grid_g=(16, 16), grid_d=(8, 8))
+
+
+@pytest.mark.parametrize("kind", ["down", "up"])
+def test_stride2_wgrad_exact_fp32_launches_every_call(K, kind):
+    """conv_s2_wgrad_f32 twice on the SAME three tensors adds the gradient twice (a memoised wrapper answered the second call without
+    launching: dW stayed at base + g).  Downsample (k = 3) / Upsample (k = 4) at N = 2, 16x16 <-> 8x8, 64 channels, integer operands
+    (x in -4..4, dy in -3..3, dW from -3..3): at most 128 * 16 terms of magnitude <= 12 per sum, so every sum is exact in fp32 in any
+    order and the result equals base + 2 g bit for bit, g from float64 autograd."""
+    g = torch.Generator().manual_seed(61)
+    N, h, C = 2, 8, 64
+    ints = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).float()          # noqa: E731
+    nh = lambda t: t.permute(0, 2, 3, 1).contiguous().to(DEV)          # noqa: E731
+    if kind == "down":
+        x, dy = ints(-4, 4, N, C, 2 * h, 2 * h), ints(-3, 3, N, C, h, h)
+        w = torch.zeros(C, C, 3, 3, dtype=torch.float64, requires_grad=True)
+        F.conv2d(x.double(), w, None, stride=2, padding=1).backward(dy.double())
+        k, tr = 3, False
+    else:
+        x, dy = ints(-4, 4, N, C, h, h), ints(-3, 3, N, C, 2 * h, 2 * h)
+        w = torch.zeros(C, C, 4, 4, dtype=torch.float64, requires_grad=True)
+        F.conv_transpose2d(x.double(), w, None, stride=2, padding=1).backward(dy.double())
+        k, tr = 4, True
+    base = ints(-3, 3, k * k * C * C).to(DEV)
+    dW, P, Q = base.clone(), nh(x), nh(dy)
+    for _ in range(2):
+        assert K.conv_s2_wgrad_f32(P, Q, dW, k=k, Ci=C, Cj=C, gather_i=not tr, grid_g=(2 * h, 2 * h), grid_d=(h, h))
+    torch.cuda.synchronize()
+    got = w_from_storage((dW - base).view(k, k, C, C), transposed=tr)
+    assert torch.equal(got.double(), 2 * w.grad), float((got.double() - 2 * w.grad).abs().max())
