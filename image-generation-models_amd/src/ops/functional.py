@@ -166,6 +166,12 @@ def _stream() -> C.c_void_p:
     return C.c_void_p(_raw_stream(_cur_dev()))
 
 
+def _count_launches(more: int):
+    """A library call that launches several kernels adds the ones behind its first (the pair head: its tests pin the kernel count)."""
+    global LAUNCHES
+    LAUNCHES += more
+
+
 LAUNCHES = 0      # library launches so far (every wrapper fetches the stream once per launch): lets a stream capture know whether a
                   # segment it is about to close recorded anything (src/runtime/graphed.py)
 
@@ -1788,6 +1794,105 @@ def latent_disc_ln_bwd(params, rec, target0, target1=0.0, c0=1.0, c1=0.0, grads=
                                     int(bool(accumulate_params)), _p(dx0), lddx, float(dx_scale), int(bool(accumulate_dx)), _stream()),
           "mi_latent_disc_ln_bwd")
     return dx0
+
+
+# --------------------------------------------------------------------------- BiGAN's pair head (pair_disc.hip)
+PAIR_DISC_H = 128
+
+
+def pair_disc_supported(N, L, H=PAIR_DISC_H, training=True) -> bool:
+    """N: rows per segment.  Training mode needs two (BatchNorm1d), evaluation mode one."""
+    return load_library().mi_pair_disc_supported(int(N), int(L), int(H), int(bool(training))) == 1
+
+
+def _pd_ptrs(ts, aligned):
+    if len(ts) != 16:
+        raise RuntimeError("pair head: sixteen parameter / gradient tensors (dis_z's ten, dis_pair's six)")
+    for t in ts:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("pair head: parameters / gradients are dense float32 tensors on the HIP device")
+        if aligned and t.data_ptr() % 16:
+            raise RuntimeError("pair head: parameter tensors are 16-byte aligned")
+    return (C.c_void_p * 16)(*[t.data_ptr() for t in ts])
+
+
+def _pd_rows(x, rows, cols, what):
+    _need_gpu(x)
+    if x.dim() != 2 or x.shape != (rows, cols) or x.stride(1) != 1 or x.dtype != torch.float32 or (rows > 1 and x.stride(0) < cols):
+        raise RuntimeError(f"{what}: float32 rows [{rows}, {cols}] with unit column stride and a pitch of at least {cols}")
+    return x.stride(0) if rows > 1 else max(cols, x.stride(0))
+
+
+def pair_disc_fwd(params, e, z, xf, loss_mode="vanilla", training=True, running_mean=None, running_var=None, num_batches_tracked=None,
+                  momentum=0.1):
+    """BiGAN's discriminator behind dis_x, on 2 N rows as two segments, and both adversarial losses, in three launches.  params: the
+    sixteen tensors in the C ABI's order (weights input-major).  e [N, L]: segment 0's code rows (the encoder's output), z [N, L]:
+    segment 1's, xf [2N, H]: dis_x's output rows; all may be pitched views, read in place.  Training mode: BatchNorm1d statistics per
+    segment, the running statistics updated twice (segment 0 first), the counter += 2.  Returns a record: logit, dlogit_g, dlogit_d
+    [2N]; g_loss, d_loss, mean_real, mean_fake, d_loss_real, d_loss_fake (device scalars); and what `pair_disc_bwd` needs."""
+    _need_gpu(e)
+    if e.dim() != 2 or z.dim() != 2 or xf.dim() != 2:
+        raise RuntimeError("pair head: e [N, L], z [N, L] and xf [2N, H] are matrices")
+    N, L = e.shape
+    lde, ldz, ldf = _pd_rows(e, N, L, "e"), _pd_rows(z, N, L, "z"), _pd_rows(xf, 2 * N, PAIR_DISC_H, "xf")
+    if z.device != e.device or xf.device != e.device:
+        raise RuntimeError("pair head: e, z and xf live on one device")
+    mode = ADV_LOSSES.get(loss_mode)
+    if mode is None:
+        raise NotImplementedError(f"loss_mode={loss_mode!r}: 'vanilla', 'lsgan' or 'hinge'")
+    lib = load_library()
+    if lib.mi_pair_disc_supported(N, L, PAIR_DISC_H, int(bool(training))) != 1:
+        check(-1, "mi_pair_disc_supported")
+    if not training and (running_mean is None or running_var is None):
+        raise RuntimeError("evaluation mode needs the running statistics")
+    for b in (running_mean, running_var):
+        if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.shape == (PAIR_DISC_H,) and b.is_contiguous()):
+            raise RuntimeError("running statistics: dense float32 [H] on the HIP device")
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise RuntimeError("num_batches_tracked: int64")
+    dev = e.device
+    tape = torch.empty(lib.mi_pair_disc_tape_floats(N, PAIR_DISC_H), device=dev, dtype=torch.float32)
+    ws = torch.empty(lib.mi_pair_disc_workspace_floats(N, PAIR_DISC_H), device=dev, dtype=torch.float32)
+    out = torch.empty((3, 2 * N), device=dev, dtype=torch.float32)
+    out6 = torch.empty(6, device=dev, dtype=torch.float32)
+    src = (N, L, PAIR_DISC_H, _p(e), lde, _p(z), ldz, _p(xf), ldf)
+    check(lib.mi_pair_disc_fwd(*src, _pd_ptrs(params, True), int(bool(training)), mode, float(momentum), _p(running_mean), _p(running_var),
+                               _p(num_batches_tracked), _p(tape), _p(ws), _p(out[0]), _p(out[1]), _p(out[2]), _p(out6), _stream()),
+          "mi_pair_disc_fwd")
+    _count_launches(2)
+    return {"N": N, "L": L, "src": src, "keep": (e, z, xf), "training": bool(training), "mode": mode, "tape": tape, "out6": out6,
+            "logit": out[0], "dlogit_g": out[1], "dlogit_d": out[2], "g_loss": out6[0], "d_loss": out6[1], "mean_real": out6[2],
+            "mean_fake": out6[3], "d_loss_real": out6[4], "d_loss_fake": out6[5]}
+
+
+def pair_disc_bwd(params, rec, dxf=None, de=None, in_scale=1.0, accumulate_in=False, grads=None, dxf_d=None, param_scale=1.0,
+                  accumulate_params=False):
+    """Backward from a `pair_disc_fwd` record.  Input gradients (from dlogit_g; dxf given): dxf [2N, H] rows (a pitched view will do)
+    and de [N, L] (optional, segment 0's code gradient) = (accumulate_in ? old : 0) + in_scale * gradient -- 2 launches, 1 without de.
+    Parameter gradients (from dlogit_d; grads given): sixteen tensors like params, g = (accumulate_params ? g : 0) + param_scale *
+    gradient, and dxf_d [2N, H] dense (optional) = d d_loss / d xf -- 3 launches.  Both in one call: 3 launches, the same bits."""
+    N, L = rec["N"], rec["L"]
+    lib = load_library()
+    if dxf is None and grads is None:
+        raise RuntimeError("pair_disc_bwd: neither input gradients (dxf) nor parameter gradients (grads) asked for")
+    if de is not None and dxf is None:
+        raise RuntimeError("pair_disc_bwd: de comes with dxf")
+    lddxf = ldde = 0
+    if dxf is not None:
+        lddxf = _pd_rows(dxf, 2 * N, PAIR_DISC_H, "dxf")
+    if de is not None:
+        ldde = _pd_rows(de, N, L, "de")
+    if dxf_d is not None:
+        _need_gpu(dxf_d)
+        if grads is None or dxf_d.shape != (2 * N, PAIR_DISC_H) or dxf_d.dtype != torch.float32 or not dxf_d.is_contiguous():
+            raise RuntimeError("dxf_d: dense float32 [2N, H], together with grads")
+    ws = torch.empty(lib.mi_pair_disc_workspace_floats(N, PAIR_DISC_H), device=rec["tape"].device, dtype=torch.float32)
+    check(lib.mi_pair_disc_bwd(*rec["src"], _pd_ptrs(params, True), int(rec["training"]), _p(rec["tape"]), _p(ws), _p(rec["dlogit_g"]),
+                               _p(rec["dlogit_d"]), _p(dxf), lddxf, _p(de), ldde, float(in_scale), int(bool(accumulate_in)),
+                               _pd_ptrs(grads, False) if grads is not None else None, _p(dxf_d), float(param_scale),
+                               int(bool(accumulate_params)), _stream()), "mi_pair_disc_bwd")
+    _count_launches((2 if grads is not None else (1 if de is not None else 0)))
+    return dxf, de
 
 
 # --------------------------------------------------------------------------- plain GAN operators (bn_seg.hip)

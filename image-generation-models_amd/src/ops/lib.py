@@ -294,6 +294,8 @@ SIGNATURES = {
     "mi_made_head_dlogits": [_I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "mi_made_head_rows": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "mi_made_sample_step": [_I, _I, _I, _P, _P, _P, _P, _I, _P],
+    "mi_pair_disc_fwd": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mi_pair_disc_bwd": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _F, _I, _P, _P, _F, _I, _P],
 }
 OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_conv3x3_wgrad_workspace": ([C.POINTER(MiWgradDesc)], C.c_size_t),
@@ -309,6 +311,9 @@ OTHER = {"mi_abi_version": ([], C.c_int), "mi_last_error": ([], C.c_char_p),
          "mi_latent_disc_workspace_floats": ([_I], C.c_size_t),
          "mi_latent_disc_ln_tape_floats": ([_I], C.c_size_t),
          "mi_latent_disc_ln_workspace_floats": ([_I], C.c_size_t),
+         "mi_pair_disc_supported": ([_I, _I, _I, _I], C.c_int),
+         "mi_pair_disc_tape_floats": ([_I, _I], C.c_size_t),
+         "mi_pair_disc_workspace_floats": ([_I, _I], C.c_size_t),
          "mi_bn_seg_workspace": ([_I, _I, _I], C.c_size_t),
          "mi_info_head_workspace_doubles": ([_I], C.c_size_t),
          "mi_age_moments_workspace_doubles": ([_I, _I], C.c_size_t),

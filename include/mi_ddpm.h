@@ -1074,6 +1074,40 @@ int mi_made_head_rows(int mode, int N, int C, int HW, int Hd, const float* h, in
 int mi_made_sample_step(int N, int C, int HW, const float* logits, int* counter, const float* uniforms, float* img, int normalize,
                         void* stream);
 
+/* ---- BiGAN's pair head (reference src/models/BiGAN.py:100-126, all of D(x, z) but dis_x's conv trunk; csrc/pair_disc.hip) ----
+ * 2 N rows as two segments (0: real pairs, 1: fake pairs), H = 128:
+ *   dis_z    code [L] -> Linear(L,H) -> GroupNorm(1,H) -> LeakyReLU(0.2) -> Linear(H,H) -> BatchNorm1d(H) per segment -> LeakyReLU
+ *            -> Linear(H,H) -> LeakyReLU = zf
+ *   dis_pair cat(zf, xf) -> Linear(2H,H) -> GroupNorm(1,H) -> LeakyReLU -> Linear(H,1) = logit
+ * e [N][lde >= L]: segment 0's code rows; z [N][ldz >= L]: segment 1's; xf [2N][ldf >= H]: dis_x's output rows.  All read in place.
+ * params / grads: sixteen pointers, weights input-major ([in][out]): dis_z's w1 [L][H], b1, gamma1, beta1, w2 [H][H], b2, gamma2, beta2
+ *   (BatchNorm1d's), w3 [H][H], b3; dis_pair's wp [2H][H], bp, gamma, beta, wc [H], bc [1].  The parameter pointers are 16-byte aligned.
+ * supported: H == 128, 1 <= L <= 128, N >= 2 per segment in training mode (N >= 1 in evaluation mode), N <= MI_PAIR_DISC_NMAX.
+ * fwd (3 launches): training: batch statistics per segment (biased variance), running_mean / running_var (nullable together) updated twice,
+ *   segment 0 first (unbiased variance), *num_batches_tracked += 2; evaluation: both segments use the running statistics, nothing is
+ *   updated.  loss_mode 0 vanilla, 1 lsgan, 2 hinge (mi_adv_loss' formulas).  Outputs, every element stored: logit [2N]; dlogit_g,
+ *   dlogit_d [2N] = d g_loss / d logit and d d_loss / d logit (g_loss: segment 0 against False + segment 1 against True; d_loss: the
+ *   opposite targets; each a sum of two per-segment means); out6 = g_loss, d_loss, mean logit of segment 0, of segment 1, d_loss' two
+ *   terms; tape (mi_pair_disc_tape_floats).  workspace: mi_pair_disc_workspace_floats floats, any content; tape and workspace 16-byte aligned.
+ * bwd, from the forward's inputs and tape, into a workspace of the same size (any content):
+ *   dxf != NULL (input gradients, from dlogit_g; 2 launches, 1 without de): dxf [2N][lddxf >= H] and de [N][ldde >= L] (nullable; segment 0's
+ *     code gradient) = (accumulate_in ? old : 0) + in_scale * gradient.  Segment 1's code gets no gradient.
+ *   grads != NULL (parameter gradients, from dlogit_d; 3 launches): g = (accumulate_params ? g : 0) + param_scale * gradient for the sixteen;
+ *     dxf_d [2N][H] dense (nullable) = d d_loss / d xf, stored.
+ *   Both in one call: 3 launches, the same bits as two calls. */
+#define MI_PAIR_DISC_NMAX (1 << 20)
+int mi_pair_disc_supported(int N, int L, int H, int training);
+size_t mi_pair_disc_tape_floats(int N, int H);
+size_t mi_pair_disc_workspace_floats(int N, int H);
+int mi_pair_disc_fwd(int N, int L, int H, const float* e, int lde, const float* z, int ldz, const float* xf, int ldf,
+                     const float* const* params, int training, int loss_mode, float momentum, float* running_mean, float* running_var,
+                     int64_t* num_batches_tracked, float* tape, float* workspace, float* logit, float* dlogit_g, float* dlogit_d, float* out6,
+                     void* stream);
+int mi_pair_disc_bwd(int N, int L, int H, const float* e, int lde, const float* z, int ldz, const float* xf, int ldf,
+                     const float* const* params, int training, const float* tape, float* workspace, const float* dlogit_g,
+                     const float* dlogit_d, float* dxf, int lddxf, float* de, int ldde, float in_scale, int accumulate_in, float* const* grads,
+                     float* dxf_d, float param_scale, int accumulate_params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
